@@ -2,6 +2,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--nodes 1000000] [--edges 20000000]
                     [--hidden 64] [--no-cpu-baseline] [--layout auto|rows|grid] [--phases C] [--return-chunks R]
+                    [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): input edges per second, forward + backward of ONE MagNetConv layer
 (K=1, q=0.25, sym normalisation, in = out = hidden, fp32), operator cached (steady state), on a DSBM
@@ -12,8 +13,12 @@ loss = out_real.sum() + out_imag.sum() and gradients w.r.t. x_real, x_imag, weig
 Timing.  W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; `value` and
 `ms_per_step` come from that wall-clock interval (max over ranks).  Every timed step is also bracketed by HIP
 events on the compute stream: `ms_per_step_median` / `_min` / `_max` are their statistics.  The per-launch
-event recorder (pygsd_prof_*) is OFF in that pass; a second, untimed pass of K steps runs with it on and feeds
-the `roofline` object (average launch duration of the dominant kernel, measured live in this run).
+event recorder (pygsd_prof_*) is OFF in that pass; a second, untimed pass of min(K, PROF_STEPS) steps runs with it on
+and feeds the `roofline` object (average launch duration of the dominant kernel, measured live in this run).  Beyond
+those, a default run does only fixed work of a few seconds (inputs, operator build, a 2 x 1 GiB copy), so its length
+follows K: a caller can size K from one run's `ms_per_step`.  `--full` adds the secondary legs -- three more K-step
+passes (dense upstream gradient, with and without its loss; exact-fp32 dense stage), the x4 DRAM-bound graph, the other
+BASELINE configurations, live PMC traffic and the CPU baseline -- about a minute more, independent of K.
 
 N > 1.  `python bench.py --gpus N` works as typed: without WORLD_SIZE in the environment it re-executes itself
 under `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL); the driver's own torchrun
@@ -22,10 +27,16 @@ parallel.ShardedMagNetConv: equal-work ranges, grid or row layout, exchanges ove
 products).  The `exchange` object reports, per step, the compute-stream time of the propagates split into
 product / exposed exchange wait / packing, and the duration of the exchanges run alone.
 
+`--dump-outputs DIR` writes what the LAST timed step handed its caller -- out_real, out_imag and the gradients of x_real,
+x_imag, weight and bias -- to DIR/<name>.npy (float32), at most DUMP_BYTES in all: the [N, F] arrays on a fixed, seeded sample
+of rows once they no longer fit whole (the same rows for every run and rank count).  The inputs depend on the arguments alone,
+so two builds of the library can be compared output for output.
+
 Extra objects in the JSON line: `roofline` (dominant kernel = the fused dual-value SpMM; algorithmic bytes per
-SURVEY.md 8(d); `achievable_peak` = a streaming float4 copy of 2 x 1 GiB timed in this run) and `cpu_baseline`
-(the oracle's reference op sequence on this box's host cores, rank 0, N=1: operator cached and, as the reference
-defaults to, rebuilt every forward).
+SURVEY.md 8(d); `achievable_peak` = a streaming float4 copy of 2 x 1 GiB timed in this run) and, with `--full`,
+`cpu_baseline` (the oracle's reference op sequence on this box's host cores, rank 0, N=1: operator cached and, as the
+reference defaults to, rebuilt every forward) and `configs`.  Without `--full` the fields of the secondary legs are null
+and `roofline.traffic` / `dram_bound_reference` are replayed from the tracked captures under profiles/, labelled so.
 """
 import argparse
 import json
@@ -42,6 +53,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_BYTES = 48 << 20  # --dump-outputs: the most written in all
+DUMP_SEED = 20240      # --dump-outputs: the row sample of the [N, F] outputs
+PROF_STEPS = 10        # steps of the instrumented pass (per-launch averages need no more)
 
 
 def spmm_bytes(nnz, n, f, s=4):
@@ -458,6 +472,36 @@ def exchange_report(args, layer_s, xr_loc, xi_loc, dist, device, world, hidden, 
     return exchange
 
 
+def dump_outputs(directory, n, row_arrays, params, rank, device, plan=None, exchange=None):
+    """--dump-outputs: `row_arrays` (name -> [rows, F] tensor: all N rows, or with `plan` this rank's local rows) and `params`
+    (name -> tensor, the same on every rank) -> directory/<name>.npy in float32, written by rank 0.  The row arrays are written
+    whole if they fit in DUMP_BYTES beside the rest, else on DUMP_SEED's sample of rows, sorted.  Sharded, every rank fills the
+    sampled rows it owns and the rows are summed over the ranks (each row is owned by exactly one)."""
+    import numpy as np
+    names = list(row_arrays)
+    widths = [row_arrays[k].size(1) for k in names]
+    fit = max(1, (DUMP_BYTES - sum(4 * p.numel() for p in params.values())) // (4 * sum(widths)))
+    if n <= fit:
+        rows = torch.arange(n)
+    else:
+        rows = torch.sort(torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))[:fit]).values
+    if plan is None:
+        idx = rows.to(device)
+        got = [row_arrays[k].detach()[idx].float() for k in names]
+    else:
+        mine = (rows >= plan.lo) & (rows < plan.hi)
+        loc = (rows[mine] - plan.lo).to(device)
+        packed = torch.zeros((rows.numel(), sum(widths)), dtype=torch.float32, device=device)
+        packed[mine.to(device)] = torch.cat([row_arrays[k].detach()[loc].float() for k in names], dim=1)
+        exchange.all_reduce(packed)
+        got = packed.split(widths, dim=1)
+    if rank != 0:
+        return
+    os.makedirs(directory, exist_ok=True)
+    for name, t in list(zip(names, got)) + list(params.items()):
+        np.save(os.path.join(directory, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def parity_guard(layer_s, xr_loc, xi_loc, x_real, x_imag, edge_index, n, hidden, rank, device):
     """Un-timed parity guard of the sharded mode: sampled rows of the sharded outputs and input gradients, and the
     all-reduced dW / db, against the UN-SHARDED HIP layer run on rank 0 with the same parameters (that layer is held
@@ -550,7 +594,17 @@ def main():
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not measure `roofline.traffic` live (two rocprofv3 --pmc passes of a short child run of this "
                          "script); the value is then replayed from profiles/pmc_traffic.json and labelled so")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: the dense-gradient and exact-fp32 passes (K steps each), the x4 "
+                         "DRAM-bound graph, the other BASELINE configurations, live PMC traffic and the CPU baseline "
+                         "(about a minute more; --no-x4 / --no-configs / --no-pmc / --no-cpu-baseline drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (out_real, out_imag, grad_x_real, "
+                         "grad_x_imag, grad_weight, grad_bias) as DIR/<name>.npy in float32, the [N, F] arrays on a fixed, "
+                         "seeded sample of rows (at most 48 MiB in all), e.g. --dump-outputs bench_outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -634,6 +688,7 @@ def main():
             x_real.grad = x_imag.grad = None
             o_r, o_i = layer(x_real, x_imag, edge_index)
             backward(o_r, o_i, loss)
+            return o_r, o_i
 
         def op_nnz():
             return layer._operator.nnz
@@ -655,6 +710,7 @@ def main():
             a.grad = b.grad = None
             o_r, o_i = ls(a, b)
             backward(o_r, o_i, loss)
+            return o_r, o_i
 
         def agree(failed: bool) -> bool:
             """True if ANY rank failed (decided over a gloo side group: it must work when RCCL does not)."""
@@ -689,7 +745,7 @@ def main():
             layer_s, xr_loc, xi_loc = make_sharded("rows", 1, 1, True)
 
         def step(loss="sum"):
-            sharded_step(layer_s, xr_loc, xi_loc, loss)
+            return sharded_step(layer_s, xr_loc, xi_loc, loss)
 
         def op_nnz():
             return layer_s.global_nnz
@@ -715,16 +771,29 @@ def main():
     sync()
     marks = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for k in range(args.steps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        step()
+        if k + 1 < args.steps:
+            step()
+        else:
+            last = step()                    # the last step's outputs (--dump-outputs); earlier ones are not kept
         b.record()
         marks.append((a, b))
     sync()
     dt = reduce_max(time.perf_counter() - t0)
     per_step = [a.elapsed_time(b) for a, b in marks]
     med = reduce_max(statistics.median(per_step))
+    if args.dump_outputs:
+        # the gradients are still the last timed step's: every step sets them anew (zero_grad(set_to_none=True))
+        lyr, xr_, xi_ = (layer, x_real, x_imag) if layer_s is None else (layer_s, xr_loc, xi_loc)
+        params = {"grad_weight": lyr.weight.grad}
+        if lyr.bias is not None:
+            params["grad_bias"] = lyr.bias.grad
+        dump_outputs(args.dump_outputs, n, {"out_real": last[0], "out_imag": last[1], "grad_x_real": xr_.grad,
+                                            "grad_x_imag": xi_.grad}, params, rank, device,
+                     plan=None if layer_s is None else layer_s.plan, exchange=None if layer_s is None else layer_s.exchange)
+    last = None
 
     # ---- pass 1b / 1c (labelled, beside the headline): the same K steps with a DENSE upstream gradient, so that the
     # headline does not lean on its loss: `out.sum()` lets the dense backward read one broadcast row (ldg = 0) where a real
@@ -739,28 +808,31 @@ def main():
         sync()
         return reduce_max(time.perf_counter() - t_begin) / args.steps * 1e3
 
-    ms_dense = timed_pass("dense")
-    ms_dense_loss = timed_pass("dense_loss")
-    dense_g.clear()
-    # ---- pass 1d (labelled): the headline's K steps with every dense product as an fp32 fmaf chain on v_mfma_f32_16x16x4_f32.
-    # The dense stage runs by default on the bf16 matrix pipe with its fp32 operands split three ways (include/pygsd_hip.h:
-    # pygsd_dense_f32_form): fp32-accurate (closer to float64 than the chain), not a reduced precision -- the
-    # line carries both so that nobody has to take that on trust.
-    from pytorch_geometric_signed_directed_amd.dense import set_dense_f32_exact
-    was_exact = set_dense_f32_exact(True)
-    try:
-        ms_exact = timed_pass("sum")
-    finally:
-        set_dense_f32_exact(was_exact)
-    step()                                   # back on the headline's loss for the instrumented pass
+    ms_dense = ms_dense_loss = ms_exact = None
+    if args.full:
+        ms_dense = timed_pass("dense")
+        ms_dense_loss = timed_pass("dense_loss")
+        dense_g.clear()
+        # ---- pass 1d (labelled): the headline's K steps with every dense product as an fp32 fmaf chain on
+        # v_mfma_f32_16x16x4_f32.  The dense stage runs by default on the bf16 matrix pipe with its fp32 operands split three
+        # ways (include/pygsd_hip.h: pygsd_dense_f32_form): fp32-accurate (closer to float64 than the chain, DESIGN.md
+        # section 7), not a reduced precision -- the line carries both so that nobody has to take that on trust.
+        from pytorch_geometric_signed_directed_amd.dense import set_dense_f32_exact
+        was_exact = set_dense_f32_exact(True)
+        try:
+            ms_exact = timed_pass("sum")
+        finally:
+            set_dense_f32_exact(was_exact)
+        step()                               # back on the headline's loss for the instrumented pass
 
     # ---- pass 2 (untimed): per-launch recorder and propagate instrumentation on.
+    prof_steps = min(args.steps, PROF_STEPS)
     _cabi.prof_reset()
     _cabi.prof_enable(True)
     if layer_s is not None:
         layer_s.engine.profile(True)
     sync()
-    for _ in range(args.steps):
+    for _ in range(prof_steps):
         step()
     sync()
     _cabi.prof_enable(False)
@@ -799,7 +871,7 @@ def main():
         achieved = alg_total / (kernel_ms * 1e-3) / 1e9 if launches else 0.0
         copy_rate = stream_copy_rate(device)
         traffic, traffic_source = None, None
-        if layer_s is None and not args.no_pmc:
+        if layer_s is None and args.full and not args.no_pmc:
             traffic, traffic_source = measure_traffic(args)
             if traffic is None:
                 traffic_source = "live PMC measurement failed (" + str(traffic_source) + "); "
@@ -825,7 +897,7 @@ def main():
             "ms_per_step_max": max(per_step),
             "value_at_median": e / (med * 1e-3),
             "ms_per_step_dense_grad": ms_dense,
-            "value_dense_grad": e / (ms_dense * 1e-3),
+            "value_dense_grad": e / (ms_dense * 1e-3) if ms_dense else None,
             "ms_per_step_dense_grad_with_loss": ms_dense_loss,
             "dense_grad_note": "same K steps, operator cached, with a dense [N, F] upstream gradient per output (g ~ N(0,1), "
                                "resident) instead of the broadcast row that `out.sum()` hands the layer: `ms_per_step_dense_grad` "
@@ -833,7 +905,7 @@ def main():
                                "(examples/magnet_node.py:22-27); `..._with_loss` = ((o_r*g_r).sum() + (o_i*g_i).sum()).backward(), "
                                "the loss's own element-wise passes timed with it",
             "ms_per_step_exact_fp32_dense": ms_exact,
-            "value_exact_fp32_dense": e / (ms_exact * 1e-3),
+            "value_exact_fp32_dense": e / (ms_exact * 1e-3) if ms_exact else None,
             "dense_arithmetic_note": "fp32 storage, fp32 accumulation everywhere.  Headline: the dense stage's products (forward and "
                                      "backward) run on the bf16 matrix pipe with each fp32 operand split into three bf16 pieces and "
                                      "the six largest partial products kept -- error vs float64 relative to the sum of |terms|: "
@@ -866,10 +938,10 @@ def main():
                          "launches": int(launches), "avg_launch_ms": avg_ms,
                          "algorithmic_bytes_per_launch": alg_total / max(launches, 1),
                          "dram_bound_reference": None},
-            "kernel_ms_per_step": {"spmm2": kernel_ms / args.steps,
-                                   **{k: v[1] / args.steps for k, v in other.items()}},
+            "kernel_ms_per_step": {"spmm2": kernel_ms / prof_steps,
+                                   **{k: v[1] / prof_steps for k, v in other.items()}},
         }
-        if world == 1 and layer_s is None and not args.no_x4:
+        if world == 1 and layer_s is None and args.full and not args.no_x4:
             # the headline's tensors are no longer needed: free them before the 4M-node graph moves in
             del layer, x_real, x_imag, edge_index
             torch.cuda.empty_cache()
@@ -880,10 +952,10 @@ def main():
             line["exchange"] = exchange
         if parity is not None:
             line["parity"] = parity
-        if world == 1 and layer_s is None and not args.no_configs:
+        if world == 1 and layer_s is None and args.full and not args.no_configs:
             torch.cuda.empty_cache()         # (the child process needs the device's memory: C4 and C5 hold 10 - 20 GB)
             line["configs"] = baseline_configs()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(hidden)
             if args.cpu_baseline_northstar:
                 try:

@@ -8,7 +8,7 @@ B="python bench.py --no-cpu-baseline --no-pmc --no-x4 --no-configs"
 O=gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o $R -- $B --steps 10 --warmup 3 > $O/prof_stats.log 2>&1
 timeout 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof_fetch -o $R -- $B --steps 3 --warmup 1 > $O/prof_fetch.log 2>&1
 timeout 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof_write -o $R -- $B --steps 3 --warmup 1 > $O/prof_write.log 2>&1
