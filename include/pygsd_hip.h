@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PYGSD_ABI_VERSION 17
+#define PYGSD_ABI_VERSION 18
 
 /* ABI version of the loaded library (== PYGSD_ABI_VERSION it was built with). */
 int pygsd_version(void);
@@ -241,6 +241,64 @@ int pygsd_sort_keys_u64_workspace(int64_t n, size_t* bytes);
 int pygsd_sort_keys_u64(const uint64_t* keys_in, uint64_t* keys_out, int32_t* perm_out,
                         int64_t n, int32_t key_bits,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sparse Gram product C = B^T diag(s) B and the row-wise intersection of two CSRs: the second-order
+ * proximity operators of DGCN (utils/directed/features_in_out.py:27-57: A_in = A^T diag(1/colsum) A,
+ * A_out = A diag(1/rowsum) A^T) and DiGCN (utils/directed/get_adjs_DiGCN.py:get_second_directed_adj:
+ * P^T P, P P^T and their intersection).  csrc/spgemm.hip.
+ * Inputs: B as CSR (b_*: rows k, int32 columns, float32 values; duplicate columns allowed, they add) and
+ * B^T as CSR (t_*: row i lists the (k, B[k, i])), both over the same entries; `scale` = s, float64 per
+ * row of B, or NULL for ones.  Output row i has n_out = number of columns of B rows.
+ * Row i has a product for every pair (entry (k, B[k,i]) of row i of B^T, entry (j, B[k,j]) of row k of B),
+ * numbered p in that order.  C[i, j] = the float64 sum, in ascending p, of (B[k,i] * s[k]) * B[k,j],
+ * rounded once to float32; a sum that is exactly 0 is not emitted; columns ascend.  Every path sums in
+ * that order, so results are bit-identical whichever path a row takes.  No float atomics.
+ * Pipeline (every call asynchronous on `stream`; the host reads two totals back):
+ *   pygsd_gram_count : count[i] = products of row i (int64).  pygsd_scan_i64 -> prod_ptr[n_out+1].
+ *   pygsd_gram_rows  : rows held in LDS, one block per row: tier 0/1/2 takes rows of at most
+ *                      pygsd_gram_tier_cap(tier) products (a row listed above its tier's cap gets
+ *                      row_nnz = -1 and is not computed; the caller rejects a negative row_nnz before
+ *                      packing).  Writes the compacted row into the temporary
+ *                      tmp_col/tmp_val (int32/float32 [prod_ptr[n_out]]) at prod_ptr[i], row_nnz[i] = its length.
+ *   pygsd_gram_hub   : rows beyond the LDS tiers (hubs), a batch at a time: hub_off[n_hub+1] = exclusive scan
+ *                      of their product counts (batch total n_products < 2^31); expand to global memory,
+ *                      stable radix sort by (hub, column), run-wise reduce.  Same outputs as pygsd_gram_rows.
+ *                      Workspace: pygsd_gram_hub_workspace(n_products) bytes.
+ *   pygsd_scan_i64(row_nnz) -> c_ptr[n_out+1]; nnz = c_ptr[n_out].
+ *   pygsd_gram_emit  : rowptr (int32 [n_out+1]), col, val of C.  nnz above 2^31 - 1 returns nonzero and
+ *                      names the limit before touching any pointer.
+ * Intersection merge (DiGCN): A, B with ascending columns per row; one wavefront per row binary-searches
+ * each entry of A in B.  An entry present in both with (a + b) != 0 (float64) is kept with (a + b) / 2.
+ *   pygsd_csr_intersect_count -> count[n_rows] (int64); pygsd_scan_i64 -> c_ptr; pygsd_csr_intersect_emit.
+ * ------------------------------------------------------------------------------------------- */
+#define PYGSD_GRAM_CAP0 1024
+#define PYGSD_GRAM_CAP1 4096
+#define PYGSD_GRAM_CAP2 8192
+int pygsd_scan_i64_workspace(int32_t n, size_t* bytes);
+int pygsd_scan_i64(const int64_t* in, int32_t n, int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
+int pygsd_gram_count(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* b_rowptr, int32_t n_out,
+                     int64_t* count, void* stream);
+int pygsd_gram_tier_cap(int32_t tier);
+int pygsd_gram_rows(const int32_t* b_rowptr, const int32_t* b_col, const float* b_val, const int32_t* t_rowptr,
+                    const int32_t* t_col, const float* t_val, const double* scale, const int32_t* rows, int32_t n_rows,
+                    int32_t tier, const int64_t* prod_ptr, int32_t* tmp_col, float* tmp_val, int64_t* row_nnz,
+                    void* stream);
+int pygsd_gram_hub_workspace(int64_t n_products, size_t* bytes);
+int pygsd_gram_hub(const int32_t* b_rowptr, const int32_t* b_col, const float* b_val, const int32_t* t_rowptr,
+                   const int32_t* t_col, const float* t_val, const double* scale, const int32_t* hub_rows,
+                   const int64_t* hub_off, int32_t n_hub, int64_t n_products, const int64_t* prod_ptr,
+                   int32_t* tmp_col, float* tmp_val, int64_t* row_nnz, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int pygsd_gram_emit(const int64_t* prod_ptr, const int32_t* tmp_col, const float* tmp_val, const int64_t* c_ptr,
+                    int32_t n_out, int64_t nnz, int32_t* rowptr, int32_t* col, float* val, void* stream);
+int pygsd_csr_intersect_count(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,
+                              const int32_t* b_rowptr, const int32_t* b_col, const float* b_val, int32_t n_rows,
+                              int64_t* count, void* stream);
+int pygsd_csr_intersect_emit(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,
+                             const int32_t* b_rowptr, const int32_t* b_col, const float* b_val, int32_t n_rows,
+                             const int64_t* c_ptr, int64_t nnz, int32_t* rowptr, int32_t* out_col, float* out_val,
+                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (Signed) magnetic Laplacian build on the device -- utils/directed/get_magnetic_Laplacian.py:47-85,

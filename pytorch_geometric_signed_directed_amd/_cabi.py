@@ -75,6 +75,19 @@ PROTOTYPES = {
     "pygsd_sort_keys_u64_workspace": (c_int32, [c_int64, ctypes.POINTER(c_size_t)]),
     "pygsd_sort_keys_u64": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_size_t,
                                       c_void_p]),
+    "pygsd_scan_i64_workspace": (c_int32, [c_int32, ctypes.POINTER(c_size_t)]),
+    "pygsd_scan_i64": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pygsd_gram_count": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pygsd_gram_tier_cap": (c_int32, [c_int32]),
+    "pygsd_gram_rows": (c_int32, [c_void_p] * 8 + [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pygsd_gram_hub_workspace": (c_int32, [c_int64, ctypes.POINTER(c_size_t)]),
+    "pygsd_gram_hub": (c_int32, [c_void_p] * 9 + [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_size_t, c_void_p]),
+    "pygsd_gram_emit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
+    "pygsd_csr_intersect_count": (c_int32, [c_void_p] * 6 + [c_int32, c_void_p, c_void_p]),
+    "pygsd_csr_intersect_emit": (c_int32, [c_void_p] * 6 + [c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                           c_void_p]),
     "pygsd_maglap_workspace": (c_int32, [c_int64, ctypes.POINTER(c_size_t)]),
     "pygsd_maglap_sort": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
     "pygsd_maglap_merge": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_size_t,
@@ -151,7 +164,7 @@ PROTOTYPES = {
     "pygsd_prof_reset": (c_int32, []),
     "pygsd_prof_collect": (c_int32, [c_int32, ctypes.POINTER(c_int64), ctypes.POINTER(c_double)]),
 }
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class PieceLayoutStruct(ctypes.Structure):

@@ -10,6 +10,8 @@ requires ("Normalized adj matrix cannot be None").  One-off host-side graph prep
     transition matrix; the reference calls a dense eigen-solver.  Up to 2000 nodes the same solver is used (exact
     parity); beyond that a sparse power iteration finds the same Perron vector.
 Results are returned on the device of `edge_index`, entries in row-major order like `torch.nonzero` yields them.
+On a CUDA `edge_index`, `get_second_directed_adj` runs on the device: the two Gram products and their intersection are
+csrc/spgemm.hip (sparse_gram), the degrees and the symmetric scaling the existing segment-sum / degree-scale kernels.
 """
 from typing import Optional, Tuple, Union
 
@@ -137,10 +139,46 @@ def get_appr_directed_adj(alpha: float, edge_index: torch.LongTensor, num_nodes:
     return _sym_normalised((half + half.T) / 2.0, edge_index.device)
 
 
+def _second_directed_adj_device(edge_index, num_nodes, edge_weight, lds_limit=None):
+    """The device path of get_second_directed_adj: P = D^-1 (A + I) (existing loops kept), L_in = P^T P and L_out = P P^T
+    as sparse Gram products, their intersection (a + b) / 2, then D^-1/2 L D^-1/2 with D = row sums."""
+    from ... import _cabi
+    from ...sparse import segment_sum_raw
+    from ...sparse_gram import SparseValues, coo_rows, from_coo, gram, intersect
+    dev = edge_index.device
+    n = int(num_nodes)
+    loops = torch.arange(n, dtype=torch.int64, device=dev)
+    row = torch.cat([edge_index[0], loops]).contiguous()
+    col = torch.cat([edge_index[1], loops]).contiguous()
+    _cabi.check_node_ids((n, row), (n, col))
+    w = (torch.ones(edge_index.size(1), dtype=torch.float32, device=dev) if edge_weight is None
+         else edge_weight.detach().to(device=dev, dtype=torch.float32))
+    w = torch.cat([w, torch.ones(n, dtype=torch.float32, device=dev)])
+    p, pt = from_coo(row, col, w, n, n)
+    deg = segment_sum_raw(p.csr.rowptr, None, p.val, n, p.csr).double()
+    inv = torch.where(deg != 0, 1.0 / torch.where(deg != 0, deg, torch.ones_like(deg)), torch.zeros_like(deg))
+    p_rows = coo_rows(p)[0]
+    p = SparseValues(p.csr, (p.val.double() * inv[p_rows]).float())
+    pt = SparseValues(pt.csr, (pt.val.double() * inv[pt.csr.col.long()]).float())
+    both = intersect(gram(p, pt, lds_limit=lds_limit), gram(pt, p, lds_limit=lds_limit))
+    index = coo_rows(both)
+    d = segment_sum_raw(both.csr.rowptr, None, both.val, n, both.csr)
+    out = torch.empty_like(both.val)
+    if both.csr.nnz:
+        with _cabi.on_device(dev):
+            _cabi.check(_cabi.lib().pygsd_degree_scale_f32(_cabi.ptr(index[0]), _cabi.ptr(index[1]), _cabi.ptr(both.val),
+                                                           _cabi.ptr(d), both.csr.nnz, 0, _cabi.ptr(out),
+                                                           _cabi.stream_ptr()), "pygsd_degree_scale_f32")
+    return index, out
+
+
 def get_second_directed_adj(edge_index: torch.LongTensor, num_nodes: Union[int, None], dtype: torch.dtype,
                             edge_weight: Optional[torch.FloatTensor] = None) -> Tuple[torch.LongTensor, torch.FloatTensor]:
     """Second-order proximity of DiGCN: L = (L_in * [L_out != 0] + L_out * [L_in != 0]) / 2 with L_in = P^T P,
-    L_out = P P^T, sym-normalised."""
+    L_out = P P^T, sym-normalised.  A CUDA `edge_index` takes the device path (same layout: row-major, ascending
+    columns, zeros dropped); a CPU one the scipy products."""
+    if edge_index.is_cuda:
+        return _second_directed_adj_device(edge_index, num_nodes, edge_weight)
     p = _transition(edge_index, edge_weight, num_nodes, dtype)
     l_in, l_out = (p.T @ p).tocsr(), (p @ p.T).tocsr()
     l_in.eliminate_zeros()
