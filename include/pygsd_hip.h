@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PYGSD_ABI_VERSION 18
+#define PYGSD_ABI_VERSION 19
 
 /* ABI version of the loaded library (== PYGSD_ABI_VERSION it was built with). */
 int pygsd_version(void);
@@ -299,6 +299,67 @@ int pygsd_csr_intersect_emit(const int32_t* a_rowptr, const int32_t* a_col, cons
                              const int32_t* b_rowptr, const int32_t* b_col, const float* b_val, int32_t n_rows,
                              const int64_t* c_ptr, int64_t nnz, int32_t* rowptr, int32_t* out_col, float* out_val,
                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * First-order PageRank operators of DiGCN (utils/directed/get_adjs_DiGCN.py:get_appr_directed_adj,
+ * Perron vector of the teleport-augmented transition matrix, and _sym_normalised) and DiGCL
+ * (cal_fast_appr / fast_appr_power).  csrc/pagerank.hip.
+ * Inputs: P (or A) and its transpose as int32 CSRs over the same entries with ASCENDING columns in
+ * every row; duplicate columns are adjacent and add.  Mode 0 ("augmented") works on float64
+ * P = D^-1 (A + I); mode 1 ("fast") on float32 A, forming D^-1 and W = (1 - alpha) A^T D^-1 in
+ * float32 as the host does.
+ * Pipeline (every call asynchronous on `stream`):
+ *   pygsd_pagerank_row_sum_f64  : out[i] = sum of row i's values in slot order (mode 0 degrees).
+ *   pygsd_pagerank_fast_prepare : mode 1: inv[i] = 1 / r_i (float32, 0 where r_i = 0; duplicates summed in
+ *                                 float32, r_i the float64 sum of the merged entries rounded once), z[i], and
+ *                                 W per slot of A^T (w_out; the first slot of each duplicate run holds the
+ *                                 entry, the others 0).
+ *   pygsd_pagerank_step         : enqueues n_steps steps of the power iteration, two launches each, over
+ *                                 M^T = (1 - alpha) P^T (val64, mode 0) or W (val32, mode 1):
+ *                                   mode 0: x <- (1 - alpha) P^T x + t / n, t <- alpha sum(x), both divided by
+ *                                           their sum; stop when |dx|_1 + |dt| < tol or after max_steps;
+ *                                   mode 1: x <- W x + c (z^T x); stop when |dx|_2 <= tol or after max_steps.
+ *                                 x (float64 [n]) holds the start vector and receives the result; y is
+ *                                 scratch [n]; work holds PYGSD_PAGERANK_WORK doubles, work[3 * PARTIALS]
+ *                                 = t (set it to the start t in mode 0).  status (int64 [2], zeroed before
+ *                                 the first step) = {stopped, completed steps}: once the rule holds every
+ *                                 further enqueued step is a no-op.  Sums are per-block partials in a fixed
+ *                                 layout summed in a fixed order: results are bit-identical run to run.
+ *   pygsd_pagerank_normalise    : pi = x / sum(x) (same deterministic sum).
+ *   pygsd_pagerank_union_count  : one wavefront per row merges row i of P and row i of P^T; entry (i, j) =
+ *                                 ((sq_i P_ij) isq_j + (sq_j P_ji) isq_i) / 2 (mode 1: (isq_i P_ji) sq_j),
+ *                                 sq = sqrt(pi), isq = pi^-1/2 as given; a zero P entry contributes nothing;
+ *                                 entries whose sum is exactly 0 are dropped (NaN is kept; mode 1 stores it
+ *                                 as 0).  Mode 1 forms P_ij = fl32(inv[i] * A_ij).  count[n] (int64);
+ *                                 pygsd_scan_i64 -> c_ptr;
+ *   pygsd_pagerank_union_emit   : rowptr (int32 [n+1]), col, val (float64) in ascending column order.  nnz
+ *                                 above 2^31 - 1 returns nonzero and names the limit before any pointer is used.
+ *   pygsd_pagerank_scale        : D^-1/2 L D^-1/2, D = row sums (inf -> 0).  Mode 0: float64, rounded once to
+ *                                 float32.  Mode 1: values rounded to float32, float32 sums in slot order and
+ *                                 float32 products.  dis: float64 [n] scratch.
+ * ------------------------------------------------------------------------------------------- */
+#define PYGSD_PAGERANK_PARTIALS 1024
+#define PYGSD_PAGERANK_WORK (3 * PYGSD_PAGERANK_PARTIALS + 2)
+int pygsd_pagerank_row_sum_f64(const int32_t* rowptr, const double* val, int32_t n, double* out, void* stream);
+int pygsd_pagerank_fast_prepare(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val,
+                                const int32_t* t_rowptr, const int32_t* t_col, const float* t_val, int32_t n,
+                                double alpha, float* inv, double* z, float* w_out, void* stream);
+int pygsd_pagerank_step(int32_t mode, const int32_t* rowptr, const int32_t* col, const double* val64,
+                        const float* val32, const double* z, int32_t n, int32_t lanes, double alpha, double c,
+                        double tol, int32_t max_steps, int32_t n_steps, double* x, double* y, double* work,
+                        int64_t work_len, int64_t* status, void* stream);
+int pygsd_pagerank_normalise(const double* x, int32_t n, double* work, int64_t work_len, double* pi, void* stream);
+int pygsd_pagerank_union_count(const int32_t* p_rowptr, const int32_t* p_col, const double* p_val64,
+                               const float* p_val32, const int32_t* t_rowptr, const int32_t* t_col,
+                               const double* t_val64, const float* t_val32, const float* inv, const double* sq,
+                               const double* isq, int32_t n, int32_t fast, int64_t* count, void* stream);
+int pygsd_pagerank_union_emit(const int32_t* p_rowptr, const int32_t* p_col, const double* p_val64,
+                              const float* p_val32, const int32_t* t_rowptr, const int32_t* t_col,
+                              const double* t_val64, const float* t_val32, const float* inv, const double* sq,
+                              const double* isq, int32_t n, int32_t fast, const int64_t* c_ptr, int64_t nnz,
+                              int32_t* rowptr, int32_t* out_col, double* out_val, void* stream);
+int pygsd_pagerank_scale(const int32_t* rowptr, const int32_t* col, const double* val, int32_t n, int32_t fast,
+                         double* dis, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (Signed) magnetic Laplacian build on the device -- utils/directed/get_magnetic_Laplacian.py:47-85,

@@ -88,6 +88,17 @@ PROTOTYPES = {
     "pygsd_csr_intersect_count": (c_int32, [c_void_p] * 6 + [c_int32, c_void_p, c_void_p]),
     "pygsd_csr_intersect_emit": (c_int32, [c_void_p] * 6 + [c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                                            c_void_p]),
+    "pygsd_pagerank_row_sum_f64": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "pygsd_pagerank_fast_prepare": (c_int32, [c_void_p] * 6 + [c_int32, c_double, c_void_p, c_void_p, c_void_p,
+                                                              c_void_p]),
+    "pygsd_pagerank_step": (c_int32, [c_int32] + [c_void_p] * 5 + [c_int32, c_int32, c_double, c_double, c_double,
+                                                                  c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                                                  c_int64, c_void_p, c_void_p]),
+    "pygsd_pagerank_normalise": (c_int32, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pygsd_pagerank_union_count": (c_int32, [c_void_p] * 11 + [c_int32, c_int32, c_void_p, c_void_p]),
+    "pygsd_pagerank_union_emit": (c_int32, [c_void_p] * 11 + [c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                                             c_void_p, c_void_p]),
+    "pygsd_pagerank_scale": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "pygsd_maglap_workspace": (c_int32, [c_int64, ctypes.POINTER(c_size_t)]),
     "pygsd_maglap_sort": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
     "pygsd_maglap_merge": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_size_t,
@@ -164,7 +175,7 @@ PROTOTYPES = {
     "pygsd_prof_reset": (c_int32, []),
     "pygsd_prof_collect": (c_int32, [c_int32, ctypes.POINTER(c_int64), ctypes.POINTER(c_double)]),
 }
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 class PieceLayoutStruct(ctypes.Structure):

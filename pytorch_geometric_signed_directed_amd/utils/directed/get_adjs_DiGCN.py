@@ -12,6 +12,8 @@ requires ("Normalized adj matrix cannot be None").  One-off host-side graph prep
 Results are returned on the device of `edge_index`, entries in row-major order like `torch.nonzero` yields them.
 On a CUDA `edge_index`, `get_second_directed_adj` runs on the device: the two Gram products and their intersection are
 csrc/spgemm.hip (sparse_gram), the degrees and the symmetric scaling the existing segment-sum / degree-scale kernels.
+`get_appr_directed_adj` and `cal_fast_appr` run on the device too (csrc/pagerank.hip via pagerank.py): a float64 power
+iteration, then a union merge of P and P^T; the augmented power iteration is used there at every n.
 """
 from typing import Optional, Tuple, Union
 
@@ -87,8 +89,19 @@ def fast_appr_power(A, alpha=0.1, max_iter=100, tol=1e-06, personalize=None):
     return L, x
 
 
+def _fast_appr_device(alpha, edge_index, num_nodes, edge_weight):
+    """The device path of cal_fast_appr (csrc/pagerank.hip): same entries, scipy's `+` semantics, NaN -> 0 and the
+    float32 degree normalisation."""
+    from ...pagerank import fast_operator
+    index, value, _, _ = fast_operator(edge_index, num_nodes, alpha, edge_weight)
+    return index, value
+
+
 def cal_fast_appr(alpha: float, edge_index: torch.LongTensor, num_nodes: Union[int, None], dtype: torch.dtype,
                   edge_weight: Optional[torch.FloatTensor] = None) -> Tuple[torch.LongTensor, torch.FloatTensor]:
+    """DiGCL's PageRank Laplacian.  A CUDA `edge_index` takes the device path; a CPU one the scipy code."""
+    if edge_index.is_cuda:
+        return _fast_appr_device(alpha, edge_index, num_nodes, edge_weight)
     r, c, w = _with_self_loops(edge_index, edge_weight, num_nodes, dtype)
     adj = sp.csr_matrix((w.astype(np.float32), (r, c)), shape=(num_nodes, num_nodes))
     L, _ = fast_appr_power(adj, alpha=alpha, tol=1e-6)
@@ -124,9 +137,21 @@ def _perron_left_vector(p, alpha: float, n: int, dense_limit: int = 2000) -> np.
     return x
 
 
+def _appr_directed_adj_device(alpha, edge_index, num_nodes, edge_weight):
+    """The device path of get_appr_directed_adj (csrc/pagerank.hip): P = D^-1 (A + I) in float64, the augmented power
+    iteration at every n, the union merge of P and P^T and the float64 symmetric normalisation."""
+    from ...pagerank import appr_operator
+    index, value, _, _ = appr_operator(edge_index, num_nodes, alpha, edge_weight)
+    return index, value
+
+
 def get_appr_directed_adj(alpha: float, edge_index: torch.LongTensor, num_nodes: Union[int, None], dtype: torch.dtype,
                           edge_weight: Optional[torch.FloatTensor] = None) -> Tuple[torch.LongTensor, torch.FloatTensor]:
-    """Approximate-PageRank Laplacian of DiGCN: L = (Pi^1/2 P Pi^-1/2 + Pi^-1/2 P^T Pi^1/2) / 2, sym-normalised."""
+    """Approximate-PageRank Laplacian of DiGCN: L = (Pi^1/2 P Pi^-1/2 + Pi^-1/2 P^T Pi^1/2) / 2, sym-normalised.
+    A CUDA `edge_index` takes the device path (same layout: row-major, ascending columns, zeros dropped); a CPU one
+    the scipy code."""
+    if edge_index.is_cuda:
+        return _appr_directed_adj_device(alpha, edge_index, num_nodes, edge_weight)
     p = _transition(edge_index, edge_weight, num_nodes, dtype)
     pi = _perron_left_vector(p, alpha, num_nodes)
     pi = pi / pi.sum()

@@ -1,0 +1,83 @@
+"""CPU: the C-ABI of the first-order PageRank operators (csrc/pagerank.hip): every entry is declared in
+include/pygsd_hip.h, exported by the built library and bound in _cabi.PROTOTYPES with the header's argument count; the
+union emit refuses an nnz beyond the int32 CSR limit before touching any pointer."""
+import ctypes
+import os
+import re
+import threading
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ("pygsd_pagerank_row_sum_f64", "pygsd_pagerank_fast_prepare", "pygsd_pagerank_step",
+           "pygsd_pagerank_normalise", "pygsd_pagerank_union_count", "pygsd_pagerank_union_emit",
+           "pygsd_pagerank_scale")
+
+
+def header_arg_counts():
+    with open(os.path.join(ROOT, "include", "pygsd_hip.h")) as f:
+        text = f.read()
+    out = {}
+    for m in re.finditer(r"^int (pygsd_pagerank_\w+)\(([^;]*)\);", text, re.M):
+        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip()])
+    return out
+
+
+def test_pagerank_entries_declared_exported_and_bound():
+    from pytorch_geometric_signed_directed_amd import _cabi
+    counts = header_arg_counts()
+    assert sorted(counts) == sorted(ENTRIES)
+    lib = ctypes.CDLL(_cabi.lib_path())
+    for name in ENTRIES:
+        assert hasattr(lib, name), name
+        assert name in _cabi.PROTOTYPES, name
+        assert len(_cabi.PROTOTYPES[name][1]) == counts[name], name
+    assert _cabi.ABI_VERSION == 19 and _cabi.lib().pygsd_version() == 19
+
+
+def test_pagerank_work_size_matches_header():
+    from pytorch_geometric_signed_directed_amd import pagerank
+    with open(os.path.join(ROOT, "include", "pygsd_hip.h")) as f:
+        text = f.read()
+    parts = int(re.search(r"#define PYGSD_PAGERANK_PARTIALS (\d+)", text).group(1))
+    assert pagerank.WORK == 3 * parts + 2
+
+
+def test_pagerank_guards_refuse_bad_arguments():
+    from pytorch_geometric_signed_directed_amd import _cabi
+    lib = _cabi.lib()
+    failures = []
+
+    def calls():   # a thread of its own: the error string is thread-local
+        try:
+            rc = lib.pygsd_pagerank_union_emit(*([None] * 11), 1, 0, None, 1 << 31, None, None, None, None)
+            assert rc != 0 and b"2^31 - 1" in lib.pygsd_last_error()
+            rc = lib.pygsd_pagerank_step(0, *([None] * 5), 4, 3, 0.1, 0.0, 1e-12, 10, 1, None, None, None, 100000, None,
+                                         None)
+            assert rc != 0 and b"lanes" in lib.pygsd_last_error()
+            rc = lib.pygsd_pagerank_step(0, *([None] * 5), 4, 4, 0.1, 0.0, 1e-12, 10, 1, None, None, None, 10, None,
+                                         None)
+            assert rc != 0 and b"work" in lib.pygsd_last_error()
+        except AssertionError as exc:
+            failures.append(exc)
+
+    t = threading.Thread(target=calls)
+    t.start()
+    t.join()
+    assert not failures, failures
+
+
+def test_lanes_follow_mean_row_length():
+    from pytorch_geometric_signed_directed_amd.pagerank import _lanes
+    assert [_lanes(nnz, 100) for nnz in (0, 100, 101, 2100, 10 ** 6)] == [1, 1, 2, 32, 64]
+
+
+def test_cpu_inputs_keep_the_host_path():
+    """A CPU edge_index never reaches the device code (it would raise without a GPU)."""
+    import numpy as np
+    import torch
+    from pytorch_geometric_signed_directed_amd.utils.directed import get_adjs_DiGCN as A
+    ei = torch.tensor([[0, 1, 2, 2], [1, 2, 0, 3]])
+    for index, value in (A.get_appr_directed_adj(0.1, ei, 5, torch.float32), A.cal_fast_appr(0.1, ei, 5, torch.float32)):
+        assert index.device.type == "cpu" and value.dtype == torch.float32
+        assert np.isfinite(value.numpy()).all()
