@@ -12,22 +12,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-inline unsigned grid_for(int64_t n, int per_block = kBlock)
-{
-    int64_t g = (n + per_block - 1) / per_block;
-    const int64_t cap = 256 * 32;  // 256 CUs x 32 blocks, grid-stride beyond
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return static_cast<unsigned>(g);
-}
-
-inline int bits_for(uint64_t max_value)
-{
-    int b = 1;
-    while (b < 64 && (max_value >> b) != 0) ++b;
-    return b;
-}
-
 __global__ void make_seg_keys(const int64_t* __restrict__ seg, int64_t n, uint32_t* __restrict__ keys,
                               uint32_t* __restrict__ ids)
 {
@@ -152,11 +136,6 @@ int sort_ws_layout(int64_t n, SortWs* w)
     w->temp_bytes = temp;
     w->total = off + 256;
     return 0;
-}
-
-inline char* align256(void* p)
-{
-    return reinterpret_cast<char*>(round_up(reinterpret_cast<uintptr_t>(p), 256));
 }
 
 }  // namespace

@@ -1,4 +1,5 @@
-// Shared host-side plumbing of libpygsd_hip.so: error string, launch checking, kernel-timing recorder.
+// Shared plumbing of libpygsd_hip.so: error string, launch checking, kernel-timing recorder, grid / workspace helpers, and the
+// device helpers more than one kernel file uses.
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -49,6 +50,40 @@ inline int check_launch(const char* what)
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---- device helpers ------------------------------------------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// eight fp32 values -> their (hi, mid, lo) bf16 pieces, round to nearest even; x - hi and x - hi - mid are exact (csrc/tall.hip)
+__device__ __forceinline__ void split8(const float (&x)[8], bf16x8 (&out)[3])
+{
+    uint32_t hh[4], mm[4], ll[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float a = x[2 * e], b = x[2 * e + 1];
+        const f32x2 v0 = {a, b};
+        hh[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v0, bf16x2));
+        const float ra = a - __uint_as_float(hh[e] << 16), rb = b - __uint_as_float(hh[e] & 0xffff0000u);
+        const f32x2 v1 = {ra, rb};
+        mm[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v1, bf16x2));
+        const float sa = ra - __uint_as_float(mm[e] << 16), sb = rb - __uint_as_float(mm[e] & 0xffff0000u);
+        const f32x2 v2 = {sa, sb};
+        ll[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v2, bf16x2));
+    }
+    out[0] = __builtin_bit_cast(bf16x8, make_uint4(hh[0], hh[1], hh[2], hh[3]));
+    out[1] = __builtin_bit_cast(bf16x8, make_uint4(mm[0], mm[1], mm[2], mm[3]));
+    out[2] = __builtin_bit_cast(bf16x8, make_uint4(ll[0], ll[1], ll[2], ll[3]));
+}
+
+// an entry of the scaled magnetic Laplacian S = 2 L / lambda_max - I: (2 x) / lam with +inf -> 0 (masked_fill_)
+__device__ __forceinline__ float scale_lam(float x, float lam)
+{
+    const float v = (2.0f * x) / lam;
+    return v == INFINITY ? 0.f : v;
+}
 
 // ---- piece layouts (include/pygsd_hip.h: pygsd_piece_layout) ------------------------------------------------------------
 // Where the 16-float pieces of row t live: `base` = element offset of the row inside slot (blk * slots_per_blk) of its chunk,
@@ -105,6 +140,25 @@ inline int piece_layout_check(const pygsd_piece_layout* L, int32_t n_rows, int32
 }
 
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// first 256-byte boundary at or after p: where a workspace's carve-up starts
+inline char* align256(void* p) { return reinterpret_cast<char*>(round_up(reinterpret_cast<uintptr_t>(p), 256)); }
+
+// blocks of a grid-stride loop over n items: ceil(n / per_block), at least 1, at most 256 CUs x 32 blocks
+inline unsigned grid_for(int64_t n, int per_block = 256)
+{
+    int64_t g = (n + per_block - 1) / per_block;
+    if (g > 256 * 32) g = 256 * 32;
+    return static_cast<unsigned>(g < 1 ? 1 : g);
+}
+
+// bits a radix-sort key needs to hold values up to max_value (at least 1)
+inline int bits_for(uint64_t max_value)
+{
+    int b = 1;
+    while (b < 64 && (max_value >> b) != 0) ++b;
+    return b;
+}
 
 // 0 = fp32 tall products / weight gradients in the split form (three bf16 pieces per value, bf16 matrix pipe) wherever a shape has
 // one, 1 = exact fp32 MFMA everywhere (csrc/tall.hip; pygsd_tall_f32_form, PYGSD_TALL_F32=exact)

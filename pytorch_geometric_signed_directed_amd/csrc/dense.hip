@@ -22,10 +22,6 @@
 namespace pygsd {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxOrder = 4;   // K + 1 <= 4
@@ -38,27 +34,6 @@ __device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c)
 }
 
 __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-// eight fp32 values -> their (hi, mid, lo) bf16 pieces, round to nearest even; x - hi and x - hi - mid are exact (csrc/tall.hip)
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8 (&out)[3])
-{
-    uint32_t hh[4], mm[4], ll[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float a = x[2 * e], b = x[2 * e + 1];
-        const f32x2 v0 = {a, b};
-        hh[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v0, bf16x2));
-        const float ra = a - __uint_as_float(hh[e] << 16), rb = b - __uint_as_float(hh[e] & 0xffff0000u);
-        const f32x2 v1 = {ra, rb};
-        mm[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v1, bf16x2));
-        const float sa = ra - __uint_as_float(mm[e] << 16), sb = rb - __uint_as_float(mm[e] & 0xffff0000u);
-        const f32x2 v2 = {sa, sb};
-        ll[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v2, bf16x2));
-    }
-    out[0] = __builtin_bit_cast(bf16x8, make_uint4(hh[0], hh[1], hh[2], hh[3]));
-    out[1] = __builtin_bit_cast(bf16x8, make_uint4(mm[0], mm[1], mm[2], mm[3]));
-    out[2] = __builtin_bit_cast(bf16x8, make_uint4(ll[0], ll[1], ll[2], ll[3]));
-}
 
 struct DenseFwdArgs {
     const float* a[kMaxOrder];

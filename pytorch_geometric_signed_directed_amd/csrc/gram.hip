@@ -25,9 +25,6 @@
 namespace pygsd {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kMaxChunks = 16;
 constexpr int kNoPart = 1 << 20;      // GramChunk::c1 / c2 of a chunk without that part
 
@@ -357,29 +354,6 @@ __global__ __launch_bounds__(256, 1) void tall_gram_bf16_wide_kernel(GramArgs p)
 // G (1.26 - 1.38 x the algorithmic bytes before, profiles/r4j_configs.json).  The loads of the next D row pairs are in flight
 // while the current D are multiplied (exact fp32, an fmaf chain over the rows in order).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-// eight fp32 values -> their (hi, mid, lo) bf16 pieces, round to nearest even; x - hi and x - hi - mid are exact (csrc/tall.hip)
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8 (&out)[3])
-{
-    uint32_t hh[4], mm[4], ll[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float a = x[2 * e], b = x[2 * e + 1];
-        const f32x2 v0 = {a, b};
-        hh[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v0, bf16x2));
-        const float ra = a - __uint_as_float(hh[e] << 16), rb = b - __uint_as_float(hh[e] & 0xffff0000u);
-        const f32x2 v1 = {ra, rb};
-        mm[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v1, bf16x2));
-        const float sa = ra - __uint_as_float(mm[e] << 16), sb = rb - __uint_as_float(mm[e] & 0xffff0000u);
-        const f32x2 v2 = {sa, sb};
-        ll[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v2, bf16x2));
-    }
-    out[0] = __builtin_bit_cast(bf16x8, make_uint4(hh[0], hh[1], hh[2], hh[3]));
-    out[1] = __builtin_bit_cast(bf16x8, make_uint4(mm[0], mm[1], mm[2], mm[3]));
-    out[2] = __builtin_bit_cast(bf16x8, make_uint4(ll[0], ll[1], ll[2], ll[3]));
-}
-
 
 constexpr int kMaxBlocks32 = 6;          // 32-column blocks of one side handled by a wavefront
 
@@ -714,9 +688,8 @@ extern "C" int pygsd_tall_gram(const void* const* xs, const int64_t* ldx, const 
     const size_t esz = dtype == 1 ? 2 : 4;
     const int vec = dtype == 1 ? 8 : 4;
     GramArgs a{};
-    // widest G chunk: 8 tiles, bf16 12 (the one-wavefront-per-SIMD instance; PYGSD_GRAM_WIDE=0 keeps 8 -- measurement / A-B)
-    const char* wide_env = getenv("PYGSD_GRAM_WIDE");
-    const int g_cap = (dtype == 1 && !(wide_env && wide_env[0] == '0')) ? 12 : 8;
+    // widest G chunk: 8 tiles, bf16 12 (the one-wavefront-per-SIMD instance)
+    const int g_cap = dtype == 1 ? 12 : 8;
     int g_whole[kMaxChunks] = {};
     int nx = 0, ng = 0, k_total = 0, f_total = 0;
     for (int s = 0; s < n_x; ++s) {

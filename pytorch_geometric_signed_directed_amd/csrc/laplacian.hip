@@ -17,20 +17,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-inline unsigned grid_for(int64_t n)
-{
-    int64_t g = (n + kBlock - 1) / kBlock;
-    if (g > 256 * 32) g = 256 * 32;
-    return static_cast<unsigned>(g < 1 ? 1 : g);
-}
-
-inline int bits_for(uint64_t v)
-{
-    int b = 1;
-    while (b < 64 && (v >> b) != 0) ++b;
-    return b;
-}
-
 #define GRID_STRIDE(i, n)                                                                  \
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < (n); \
          i += static_cast<int64_t>(gridDim.x) * blockDim.x)
@@ -169,12 +155,6 @@ __global__ __launch_bounds__(256) void long_row_sums(const int32_t* __restrict__
 // same |.|, conjugate phase, multiplied in the mirrored entry's own order), so there is no lookup.
 // Scaling S = 2 L / lambda_max - I is folded in: v = (2 x) / lam with +inf -> 0 (masked_fill_), diag - 1.
 // Replaces two radix sorts + six gathers of the generic COO -> CSR route.
-__device__ __forceinline__ float scale_lam(float x, float lam)
-{
-    const float v = (2.0f * x) / lam;
-    return v == INFINITY ? 0.f : v;
-}
-
 __global__ void assemble_csr(const int64_t* __restrict__ row, const int64_t* __restrict__ col,
                              const float* __restrict__ off_re, const float* __restrict__ off_im,
                              const float* __restrict__ mir_re, const float* __restrict__ mir_im,
@@ -354,11 +334,6 @@ int lap_layout(int64_t e, LapWs* w)
     w->scan_tmp_bytes = scan_tmp;
     w->total = off + 256;
     return 0;
-}
-
-inline char* align256(void* p)
-{
-    return reinterpret_cast<char*>(round_up(reinterpret_cast<uintptr_t>(p), 256));
 }
 
 struct LoopWs {

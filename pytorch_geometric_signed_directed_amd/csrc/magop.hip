@@ -40,20 +40,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kBlockRowMax = 4096;     // rows up to this many symmetrised entries are sorted by one block in LDS
 
-inline unsigned grid_for(int64_t n)
-{
-    int64_t g = (n + kBlock - 1) / kBlock;
-    if (g > 256 * 32) g = 256 * 32;
-    return static_cast<unsigned>(g < 1 ? 1 : g);
-}
-
-inline int bits_for(uint64_t v)
-{
-    int b = 1;
-    while (b < 64 && (v >> b) != 0) ++b;
-    return b;
-}
-
 #define GRID_STRIDE(i, n)                                                                  \
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < (n); \
          i += static_cast<int64_t>(gridDim.x) * blockDim.x)
@@ -257,7 +243,6 @@ __device__ __forceinline__ float degree_source(float s, float a, int deg_mode)
 //   y = A_s (fp32 bits), z = Theta_arg (fp32 bits)
 //   w = row | (1 << 31 if the row's diagonal goes right BEFORE this entry), or kNoEntry behind a row's distinct entries
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kNoEntry = 0xFFFFFFFFu;
 constexpr uint32_t kFlag = 0x80000000u;
 
@@ -579,12 +564,6 @@ __device__ __forceinline__ uint4 load_record(const uint4* __restrict__ ent, int6
 {
     const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ent) + p);     // touched once
     return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ float scale_lam(float x, float lam)
-{
-    const float v = (2.0f * x) / lam;
-    return v == INFINITY ? 0.f : v;
 }
 
 // Values of S = 2 L / lambda_max + diag_shift I in the final CSR slots, one thread per record of the stream.
@@ -1836,11 +1815,6 @@ int magop_layout(int64_t e, int32_t n, int weighted, MagopWs* w)
     w->scan_tmp_bytes = scan_tmp;
     w->total = off + 256;
     return 0;
-}
-
-inline char* align256(void* p)
-{
-    return reinterpret_cast<char*>(round_up(reinterpret_cast<uintptr_t>(p), 256));
 }
 
 }  // namespace

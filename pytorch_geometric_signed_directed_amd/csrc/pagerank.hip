@@ -36,14 +36,6 @@ inline unsigned blocks_for(int64_t items, int64_t per_block)
     return static_cast<unsigned>(g);
 }
 
-inline unsigned grid_rows(int64_t n, int per_block = kThreads)
-{
-    int64_t g = (n + per_block - 1) / per_block;
-    if (g > 256 * 32) g = 256 * 32;
-    if (g < 1) g = 1;
-    return static_cast<unsigned>(g);
-}
-
 // Sum over the block in a fixed order (wave butterfly, then the wave sums in wave order); every thread gets it.
 __device__ double block_sum(double v, double* lds)
 {
@@ -391,7 +383,7 @@ extern "C" int pygsd_pagerank_row_sum_f64(const int32_t* rowptr, const double* v
     PYGSD_REQUIRE(rowptr && val && out, "pygsd_pagerank_row_sum_f64: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     ProfScope prof(PYGSD_K_BUILD, s);
-    hipLaunchKernelGGL(pr_row_sum_kernel, dim3(grid_rows(n)), dim3(kThreads), 0, s, rowptr, val, n, out);
+    hipLaunchKernelGGL(pr_row_sum_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, rowptr, val, n, out);
     return check_launch("pr_row_sum_kernel");
 }
 
@@ -405,10 +397,10 @@ extern "C" int pygsd_pagerank_fast_prepare(const int32_t* a_rowptr, const int32_
     hipStream_t s = static_cast<hipStream_t>(stream);
     ProfScope prof(PYGSD_K_BUILD, s);
     const double z_nz = alpha * (1 + alpha), z_zero = (1 - alpha) / (1 + alpha) + alpha * (1 + alpha);
-    hipLaunchKernelGGL(pr_fast_rows_kernel, dim3(grid_rows(n)), dim3(kThreads), 0, s, a_rowptr, a_col, a_val, n, z_nz,
+    hipLaunchKernelGGL(pr_fast_rows_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, a_rowptr, a_col, a_val, n, z_nz,
                        z_zero, inv, z);
     if (int rc = check_launch("pr_fast_rows_kernel")) return rc;
-    hipLaunchKernelGGL(pr_fast_weights_kernel, dim3(grid_rows(n)), dim3(kThreads), 0, s, t_rowptr, t_col, t_val, n,
+    hipLaunchKernelGGL(pr_fast_weights_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, t_rowptr, t_col, t_val, n,
                        static_cast<float>(1 - alpha), inv, w_out);
     return check_launch("pr_fast_weights_kernel");
 }
@@ -467,7 +459,7 @@ static int union_launch(const int32_t* p_rowptr, const int32_t* p_col, const dou
     UnionArgs u{p_rowptr, t_rowptr, {p_col, fast ? nullptr : p_val64, fast ? p_val32 : nullptr},
                 {t_col, fast ? nullptr : t_val64, fast ? t_val32 : nullptr}, inv, sq, isq, n, fast, count, c_ptr,
                 rowptr, out_col, out_val};
-    hipLaunchKernelGGL(pr_union_kernel, dim3(grid_rows(static_cast<int64_t>(n) + 1, kWaves)), dim3(kThreads), 0, s, u,
+    hipLaunchKernelGGL(pr_union_kernel, dim3(grid_for(static_cast<int64_t>(n) + 1, kWaves)), dim3(kThreads), 0, s, u,
                        emit);
     return check_launch("pr_union_kernel");
 }
@@ -514,8 +506,8 @@ extern "C" int pygsd_pagerank_scale(const int32_t* rowptr, const int32_t* col, c
     PYGSD_REQUIRE(rowptr && col && val && dis && out, "pygsd_pagerank_scale: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     ProfScope prof(PYGSD_K_BUILD, s);
-    hipLaunchKernelGGL(pr_degree_kernel, dim3(grid_rows(n)), dim3(kThreads), 0, s, rowptr, val, n, fast, dis);
+    hipLaunchKernelGGL(pr_degree_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, rowptr, val, n, fast, dis);
     if (int rc = check_launch("pr_degree_kernel")) return rc;
-    hipLaunchKernelGGL(pr_apply_kernel, dim3(grid_rows(n)), dim3(kThreads), 0, s, rowptr, col, val, n, fast, dis, out);
+    hipLaunchKernelGGL(pr_apply_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, rowptr, col, val, n, fast, dis, out);
     return check_launch("pr_apply_kernel");
 }

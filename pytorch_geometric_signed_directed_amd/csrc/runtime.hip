@@ -2,8 +2,6 @@
 // pygsd_last_error, pygsd_prof_*).
 #include "common.hpp"
 
-#include <cstdlib>
-
 namespace pygsd {
 
 std::string& last_error()
@@ -74,27 +72,23 @@ using namespace pygsd;
 namespace {
 constexpr int kBlock = 256;
 
-// Streaming copy, 16 bytes per lane, non-temporal both ways: the achievable-HBM yardstick bench.py prices
-// the gather kernels against (MI355X_MICROARCH.md: "6.29 TB/s measured (float4 copy)").
-typedef float vec4f __attribute__((ext_vector_type(4)));
+// Streaming copy, 16 bytes per lane, plain loads and stores: the achievable-HBM yardstick bench.py prices
+// the gather kernels against (MI355X_MICROARCH.md: "6.29 TB/s measured (float4 copy)").  kCopyUnroll float4 per lane are in
+// flight before the first store only once the grid is capped at kCopyMaxBlocks (beyond 2^40 bytes).
+constexpr int kCopyUnroll = 4;
+constexpr int64_t kCopyMaxBlocks = int64_t(256) << 20;
 
-// MODE bit 0: non-temporal loads, bit 1: non-temporal stores.  UN float4 per lane in flight before the first store.
-template <int MODE, int UN>
-__global__ __launch_bounds__(kBlock) void stream_copy_kernel(const vec4f* __restrict__ src,
-                                                            vec4f* __restrict__ dst, int64_t n4)
+__global__ __launch_bounds__(kBlock) void stream_copy_kernel(const f32x4* __restrict__ src,
+                                                            f32x4* __restrict__ dst, int64_t n4)
 {
     const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
     int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    for (; i + (UN - 1) * stride < n4; i += UN * stride) {
-        vec4f v[UN];
+    for (; i + (kCopyUnroll - 1) * stride < n4; i += kCopyUnroll * stride) {
+        f32x4 v[kCopyUnroll];
 #pragma unroll
-        for (int u = 0; u < UN; ++u)
-            v[u] = (MODE & 1) ? __builtin_nontemporal_load(src + i + u * stride) : src[i + u * stride];
+        for (int u = 0; u < kCopyUnroll; ++u) v[u] = src[i + u * stride];
 #pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            if (MODE & 2) __builtin_nontemporal_store(v[u], dst + i + u * stride);
-            else dst[i + u * stride] = v[u];
-        }
+        for (int u = 0; u < kCopyUnroll; ++u) dst[i + u * stride] = v[u];
     }
     for (; i < n4; i += stride) dst[i] = src[i];
 }
@@ -210,25 +204,13 @@ extern "C" int pygsd_stream_copy_f32(const float* src, float* dst, int64_t n, vo
     hipStream_t s = static_cast<hipStream_t>(stream);
     ProfScope prof(PYGSD_K_ELEMENTWISE, s);
     const int64_t n4 = n / 4;
-    // Defaults = the fastest shape of tools/copy_probe.py on MI355X (profiles/r2_copy_probe.json): plain loads and
-    // stores, ONE float4 per lane over an uncapped grid (the unrolled main loop never runs then) -- 6.16 TB/s (persistent grids of 4..64 blocks per
-    // CU and non-temporal variants: 4.2..5.4 TB/s; torch's copy_: 4.55 TB/s).  PYGSD_COPY_MODE (0 plain, 1 nt loads,
-    // 2 nt stores, 3 both) and PYGSD_COPY_BLOCKS_PER_CU exist for that probe only.
-    const char* m = getenv("PYGSD_COPY_MODE");
-    const char* b = getenv("PYGSD_COPY_BLOCKS_PER_CU");
-    const int mode = m ? atoi(m) : 0;
-    const int64_t per_cu = b ? atoi(b) : (int64_t(1) << 20);
+    // The fastest shape measured on MI355X (profiles/r2_copy_probe.json): plain loads and stores, ONE float4 per lane over an
+    // uncapped grid (the unrolled main loop never runs then) -- 6.16 TB/s (persistent grids of 4..64 blocks per CU and
+    // non-temporal variants: 4.2..5.4 TB/s; torch's copy_: 4.55 TB/s).
     int64_t blocks = (n4 + kBlock - 1) / kBlock;
-    if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
-    const vec4f* sp = reinterpret_cast<const vec4f*>(src);
-    vec4f* dp = reinterpret_cast<vec4f*>(dst);
-    switch (mode & 3) {
-        case 0: hipLaunchKernelGGL((stream_copy_kernel<0, 4>), grid, block, 0, s, sp, dp, n4); break;
-        case 1: hipLaunchKernelGGL((stream_copy_kernel<1, 4>), grid, block, 0, s, sp, dp, n4); break;
-        case 2: hipLaunchKernelGGL((stream_copy_kernel<2, 4>), grid, block, 0, s, sp, dp, n4); break;
-        default: hipLaunchKernelGGL((stream_copy_kernel<3, 4>), grid, block, 0, s, sp, dp, n4); break;
-    }
+    if (blocks > kCopyMaxBlocks) blocks = kCopyMaxBlocks;
+    hipLaunchKernelGGL(stream_copy_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s,
+                       reinterpret_cast<const f32x4*>(src), reinterpret_cast<f32x4*>(dst), n4);
     return check_launch("stream_copy_kernel");
 }
 
@@ -325,9 +307,9 @@ extern "C" int pygsd_gather_pieces_f32(const float* const* srcs, const pygsd_pie
 
 namespace {
 struct WeightedSumArgs {
-    const vec4f* x[8];
+    const f32x4* x[8];
     float w[8];
-    vec4f* out;
+    f32x4* out;
     int64_t n4, ldo4;    // float4 units: elements in total, output row stride
     int32_t k, c4;       // operands, float4 units per row
 };
@@ -338,7 +320,7 @@ __global__ __launch_bounds__(256) void weighted_sum_kernel(WeightedSumArgs a)
 {
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < a.n4;
          i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-        vec4f acc = a.x[0][i] * a.w[0];
+        f32x4 acc = a.x[0][i] * a.w[0];
         for (int j = 1; j < a.k; ++j) acc += a.x[j][i] * a.w[j];       // the reference's accumulation order
         const int64_t r = i / a.c4;
         a.out[r * a.ldo4 + (i - r * a.c4)] = acc;
@@ -348,8 +330,8 @@ __global__ __launch_bounds__(256) void weighted_sum_kernel(WeightedSumArgs a)
 constexpr int kDotBlocks = 1024;     // at most; fewer where the workspace does not hold blocks x k float64 partials
 
 struct DotsArgs {
-    const vec4f* g;
-    const vec4f* x[8];
+    const f32x4* g;
+    const f32x4* x[8];
     double* partial;     // [gridDim.x][k]
     int64_t n4, ldg4;
     int32_t k, c4;
@@ -372,12 +354,12 @@ __global__ __launch_bounds__(256) void dots_kernel(DotsArgs a)
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < a.n4;
          i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
         const int64_t r = i / a.c4;
-        const vec4f g = a.g[r * a.ldg4 + (i - r * a.c4)];
+        const f32x4 g = a.g[r * a.ldg4 + (i - r * a.c4)];
         const double g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             if (j < a.k) {
-                const vec4f x = a.x[j][i];
+                const f32x4 x = a.x[j][i];
                 acc[j] = fma(g0, static_cast<double>(x[0]), acc[j]);
                 acc[j] = fma(g1, static_cast<double>(x[1]), acc[j]);
                 acc[j] = fma(g2, static_cast<double>(x[2]), acc[j]);
@@ -427,10 +409,10 @@ extern "C" int pygsd_weighted_sum_f32(const float* const* xs, const float* weigh
     WeightedSumArgs a{};
     for (int j = 0; j < k; ++j) {
         PYGSD_REQUIRE(xs[j] && aligned16(xs[j]), "pygsd_weighted_sum_f32: operand %d null or not 16-byte aligned", j);
-        a.x[j] = reinterpret_cast<const vec4f*>(xs[j]);
+        a.x[j] = reinterpret_cast<const f32x4*>(xs[j]);
         a.w[j] = weights[j];                                           // HOST array: the weights travel by value
     }
-    a.out = reinterpret_cast<vec4f*>(out);
+    a.out = reinterpret_cast<f32x4*>(out);
     a.c4 = n_cols / 4;
     a.n4 = n_rows * a.c4;
     a.ldo4 = ldo / 4;
@@ -460,9 +442,9 @@ extern "C" int pygsd_dots_f32(const float* g, int64_t ldg, const float* const* x
     DotsArgs a{};
     for (int j = 0; j < k; ++j) {
         PYGSD_REQUIRE(xs[j] && aligned16(xs[j]), "pygsd_dots_f32: operand %d null or not 16-byte aligned", j);
-        a.x[j] = reinterpret_cast<const vec4f*>(xs[j]);
+        a.x[j] = reinterpret_cast<const f32x4*>(xs[j]);
     }
-    a.g = reinterpret_cast<const vec4f*>(g);
+    a.g = reinterpret_cast<const f32x4*>(g);
     a.partial = static_cast<double*>(workspace);
     a.c4 = n_cols / 4;
     a.n4 = n_rows * a.c4;

@@ -23,24 +23,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-inline unsigned grid_for(int64_t n, int per_block = kBlock)
-{
-    int64_t g = (n + per_block - 1) / per_block;
-    const int64_t cap = 256 * 32;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return static_cast<unsigned>(g);
-}
-
-inline int bits_for(uint64_t max_value)
-{
-    int b = 1;
-    while (b < 64 && (max_value >> b) != 0) ++b;
-    return b;
-}
-
-inline char* align256(void* p) { return reinterpret_cast<char*>(round_up(reinterpret_cast<uintptr_t>(p), 256)); }
-
 // the value of one product, computed the same way on every path: (B[k, i] * s[k]) * B[k, j] in float64
 __device__ __forceinline__ double row_factor(float t_val, const double* scale, int k)
 {

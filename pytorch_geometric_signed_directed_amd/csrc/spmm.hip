@@ -215,124 +215,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void spmm_vec_kernel(SpmmArgs 
 }
 
 // ------------------------------------------------------------------------------------------
-// K = 1 magnetic layer, forward, F_in = F_out = 64 (the north-star shape): the dense stage in the dual SpMM's epilogue.
-//   T1_r = S_r^T x_r, T1_i = S_i^T x_i (written: the backward needs them)
-//   out_real = (x_r - x_i) W_0 + (T1_r - T1_i) W_1 + b ,  out_imag = (x_r + x_i) W_0 + (T1_r + T1_i) W_1 + b
-// (MagNetConv.py:189-247 for K = 1).  After the butterfly every lane group holds the row's two products; the 64 lanes
-// then compute one output column each: 128 features are broadcast with v_readlane (an SGPR operand of the FMA), W sits in LDS
-// ([128][64], lane j reads column j: conflict-free), 256 FMAs per lane on a kernel whose VALU is idle two thirds of the time
-// (it is bound by the gathers).  Saves the separate dense pass' re-read of T1 and a launch; costs LDS (32 KB per block) and
-// ~600 VALU instructions per row.  Behind PYGSD_FUSE_K1 / dense.set_fused_k1 -- measured both ways, see DESIGN.md.
-// ------------------------------------------------------------------------------------------
-struct SpmmK1Args {
-    SpmmArgs s;
-    const float* w;         // [2][64][64]
-    const float* bias;      // [64] or null
-    float* out_r;
-    float* out_i;
-    int64_t ldo;
-};
-
-template <bool DEEP>
-__global__ __launch_bounds__(kWavesPerBlock * 64) void spmm2_k1_dense_kernel(SpmmK1Args q)
-{
-    constexpr int LPR = 16, NPW = 4;
-    constexpr int UB = DEEP ? 8 : 2;
-    __shared__ float wl[128 * 64];
-    const SpmmArgs& p = q.s;
-    for (int i = threadIdx.x; i < 128 * 64; i += kWavesPerBlock * 64) wl[i] = q.w[i];
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int row = __builtin_amdgcn_readfirstlane(
-        static_cast<int>(blockIdx.x) * kWavesPerBlock + static_cast<int>(threadIdx.x >> 6));
-    if (row >= p.n_rows) return;
-    const int sub = lane / LPR;
-    const int fl = (lane % LPR) * 4;
-    const int beg = p.rowptr[row];
-    const int end = p.rowptr[row + 1];
-    float4 acc_a = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 acc_b = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* xa = p.xa + fl;
-    const float* xb = p.xb + fl;
-    __shared__ float4 lvl2[kWavesPerBlock * 64 * 2];
-    float4* slot = lvl2 + threadIdx.x * 2;
-    const bool multi = end - beg > 64;
-    for (int base = beg; base < end; base += 64) {
-        const int cnt = (end - base) < 64 ? (end - base) : 64;
-        int c = 0;
-        float wa = 0.f, wb = 0.f;
-        if (lane < cnt) {
-            c = __builtin_nontemporal_load(p.col + base + lane);
-            wa = __builtin_nontemporal_load(p.va + base + lane);
-            wb = __builtin_nontemporal_load(p.vb + base + lane);
-        }
-        int u = 0;
-        for (; cnt - u >= NPW * UB; u += NPW * UB)
-            gather_step<LPR, true, UB>(u, cnt, sub, true, c, wa, wb, xa, xb, p.ldx, acc_a, acc_b);
-        if (UB >= 8 && cnt - u >= NPW * (UB / 2)) {
-            gather_step<LPR, true, (UB >= 8 ? UB / 2 : 1)>(u, cnt, sub, true, c, wa, wb, xa, xb, p.ldx, acc_a, acc_b);
-            u += NPW * (UB / 2);
-        }
-        for (; u < cnt; u += NPW * 2)
-            gather_step<LPR, true, 2>(u, cnt, sub, true, c, wa, wb, xa, xb, p.ldx, acc_a, acc_b);
-        if (multi) {                                    // (the same second level as spmm_vec_kernel: bitwise the composed path)
-            flush_level(slot[0], acc_a, base == beg);
-            flush_level(slot[1], acc_b, base == beg);
-        }
-    }
-    if (multi) {
-        acc_a = slot[0];
-        acc_b = slot[1];
-    }
-    // the row's own features (T_0): loaded behind the gather loop, so that the loop keeps the plain kernel's register count
-    // (and with it 4 wavefronts per SIMD); their latency overlaps the butterfly and the T_1 stores
-    const float4 x0a = ld4(xa + static_cast<int64_t>(row) * p.ldx);
-    const float4 x0b = ld4(xb + static_cast<int64_t>(row) * p.ldx);
-    reduce_groups<LPR>(acc_a);
-    reduce_groups<LPR>(acc_b);
-    if (sub == 0) {
-        const int64_t yo = static_cast<int64_t>(row) * p.ldy + fl;
-        st4(p.ya + yo, acc_a);
-        st4(p.yb + yo, acc_b);
-    }
-    // lane group 0 (lanes 0..15) holds feature quads 0..15 of all four 64-vectors
-    const float d0[4] = {x0a.x - x0b.x, x0a.y - x0b.y, x0a.z - x0b.z, x0a.w - x0b.w};
-    const float s0[4] = {x0a.x + x0b.x, x0a.y + x0b.y, x0a.z + x0b.z, x0a.w + x0b.w};
-    const float d1[4] = {acc_a.x - acc_b.x, acc_a.y - acc_b.y, acc_a.z - acc_b.z, acc_a.w - acc_b.w};
-    const float s1[4] = {acc_a.x + acc_b.x, acc_a.y + acc_b.y, acc_a.z + acc_b.z, acc_a.w + acc_b.w};
-    float o_r = 0.f, o_i = 0.f;
-    const float* wcol = wl + lane;                                  // column j = lane of W_0 (rows 0..63) and W_1 (64..127)
-    // (partially unrolled: fully unrolled, the 128 LDS reads are hoisted in front of the FMAs and the kernel needs 150 VGPRs --
-    // one wavefront per SIMD fewer than the plain dual kernel, whose occupancy is what the gathers live on)
-#pragma unroll 2
-    for (int qd = 0; qd < 16; ++qd) {
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            const float w0 = wcol[(4 * qd + cc) * 64];
-            const float dv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d0[cc]), qd));
-            const float sv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s0[cc]), qd));
-            o_r = fmaf(dv, w0, o_r);
-            o_i = fmaf(sv, w0, o_i);
-        }
-    }
-#pragma unroll 2
-    for (int qd = 0; qd < 16; ++qd) {
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            const float w1 = wcol[(64 + 4 * qd + cc) * 64];
-            const float dv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d1[cc]), qd));
-            const float sv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s1[cc]), qd));
-            o_r = fmaf(dv, w1, o_r);
-            o_i = fmaf(sv, w1, o_i);
-        }
-    }
-    const float bj = q.bias ? q.bias[lane] : 0.f;
-    const int64_t oo = static_cast<int64_t>(row) * q.ldo + lane;
-    q.out_r[oo] = o_r + bj;
-    q.out_i[oo] = o_i + bj;
-}
-
-// ------------------------------------------------------------------------------------------
 // Hub rows (power-law tails).  One wavefront per row makes a row with 10^5..10^6 entries the critical path
 // (27 us per 1000 entries: 27 ms for a 1M-entry hub against 0.14 ms for the rest of a 4M-entry operator).
 // Rows longer than PYGSD_LONG_ROW entries are therefore skipped by the main kernel and handled here:
@@ -544,65 +426,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void spmm_packed_kernel(SpmmAr
     }
 }
 
-// The first version (kept for A/B probes, PYGSD_SPMM_PACKED_V1=1): every group loads its own row's col / val inside its loop.
-template <int LPR, bool DUAL>
-__global__ __launch_bounds__(kWavesPerBlock * 64) void spmm_packed_v1_kernel(SpmmArgs p)
-{
-    constexpr int NPW = 64 / LPR;
-    constexpr int UN = 4;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane / LPR;
-    const int fl = (lane % LPR) * 4;
-    const int64_t wave = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t row = wave * NPW + sub;
-    const bool fact = fl < p.n_feat;
-    int beg = 0, end = 0;
-    bool mine = row < p.n_rows;
-    if (mine) {
-        beg = p.rowptr[row];
-        end = p.rowptr[row + 1];
-        if (p.skip_longer_than > 0 && end - beg > p.skip_longer_than) {   // hub row: spmm_long_kernel
-            mine = false;
-            end = beg;
-        }
-    }
-    const int deg = end - beg;
-    float4 acc_a = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 acc_b = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* xa = p.xa + fl;
-    const float* xb = DUAL ? p.xb + fl : nullptr;
-    for (int e = beg; e < end; e += UN) {
-        int cj[UN];
-        float wa[UN], wb[UN];
-        float4 ga[UN], gb[UN];
-#pragma unroll
-        for (int k = 0; k < UN; ++k) {
-            const bool ok = e + k < end;
-            cj[k] = ok ? __builtin_nontemporal_load(p.col + e + k) : 0;
-            wa[k] = ok ? (p.va ? __builtin_nontemporal_load(p.va + e + k) : 1.f) : 0.f;
-            wb[k] = (DUAL && ok) ? __builtin_nontemporal_load(p.vb + e + k) : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < UN; ++k) {
-            const bool ok = fact && e + k < end;
-            const int64_t off = static_cast<int64_t>(cj[k]) * p.ldx;
-            ga[k] = ok ? ld4(xa + off) : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (DUAL) gb[k] = ok ? ld4(xb + off) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int k = 0; k < UN; ++k) {
-            fma4(acc_a, wa[k], ga[k]);
-            if (DUAL) fma4(acc_b, wb[k], gb[k]);
-        }
-    }
-    if (mine && fact) {
-        const int64_t yo = row * p.ldy + fl;
-        const int64_t zo = row * p.ldz + fl;
-        st4(p.ya + yo, finish(acc_a, p.alpha, p.beta, p.mean != 0, deg, p.za ? p.za + zo : nullptr));
-        if (DUAL) st4(p.yb + yo, finish(acc_b, p.alpha, p.beta, false, deg, p.zb ? p.zb + zo : nullptr));
-    }
-}
-
 // Generic fallback (any F, any alignment): lane <-> feature, neighbours walked sequentially with
 // wave-uniform (scalar) col/val loads, 256-byte coalesced row reads.
 template <bool DUAL>
@@ -721,23 +544,14 @@ int launch_spmm(SpmmArgs a, int64_t nnz_hint, const pygsd_long_rows* hubs, hipSt
     bool packed = false;
     if (lpr <= 32) {
         const char* force = getenv("PYGSD_SPMM_PACKED");
-        const char* upto = getenv("PYGSD_SPMM_PACKED_BELOW");       // probes: entries per row below which rows are packed
-        const int64_t thr = upto ? atoll(upto) : packed_threshold(lpr, DUAL);
         if (force) packed = force[0] == '1';
-        else packed = nnz_hint > 0 && nnz_hint < thr * static_cast<int64_t>(a.n_rows);
+        else packed = nnz_hint > 0 && nnz_hint < packed_threshold(lpr, DUAL) * static_cast<int64_t>(a.n_rows);
     }
     if (packed) {
         const int npw = 64 / lpr;
         const int64_t waves = (static_cast<int64_t>(a.n_rows) + npw - 1) / npw;
         const dim3 pg(static_cast<unsigned>((waves + kWavesPerBlock - 1) / kWavesPerBlock));
-        const char* v1env = getenv("PYGSD_SPMM_PACKED_V1");
-        const bool v1 = v1env && v1env[0] == '1';
-        if (v1) {
-            if (lpr == 4) hipLaunchKernelGGL((spmm_packed_v1_kernel<4, DUAL>), pg, block, 0, stream, a);
-            else if (lpr == 8) hipLaunchKernelGGL((spmm_packed_v1_kernel<8, DUAL>), pg, block, 0, stream, a);
-            else if (lpr == 16) hipLaunchKernelGGL((spmm_packed_v1_kernel<16, DUAL>), pg, block, 0, stream, a);
-            else hipLaunchKernelGGL((spmm_packed_v1_kernel<32, DUAL>), pg, block, 0, stream, a);
-        } else if (lpr == 4) hipLaunchKernelGGL((spmm_packed_kernel<4, DUAL>), pg, block, 0, stream, a);
+        if (lpr == 4) hipLaunchKernelGGL((spmm_packed_kernel<4, DUAL>), pg, block, 0, stream, a);
         else if (lpr == 8) hipLaunchKernelGGL((spmm_packed_kernel<8, DUAL>), pg, block, 0, stream, a);
         else if (lpr == 16) hipLaunchKernelGGL((spmm_packed_kernel<16, DUAL>), pg, block, 0, stream, a);
         else hipLaunchKernelGGL((spmm_packed_kernel<32, DUAL>), pg, block, 0, stream, a);
@@ -788,12 +602,10 @@ __device__ __forceinline__ float bf16_to_f32(uint32_t h) { return __uint_as_floa
 // two fp32 -> two bf16 in one dword, round to nearest even: ONE v_cvt_pk_bf16_f32 on gfx950 (the integer formulation --
 // NaN test, bias add, shift -- costs 6 VALU instructions per value, and this kernel is instruction-issue bound on
 // short bf16 rows: ~330 instructions per 26-entry row at 4 cycles each = the measured 1.1 ms at 2M rows)
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi)
 {
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
+    const f32x2 v = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
 }
 __device__ __forceinline__ void unpack8(const uint4& q, float (&v)[8])
 {
@@ -847,7 +659,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void spmm_vec_bf16_kernel(Spmm
     const bool fact = fl < p.n_feat;
     const int beg = p.rowptr[row];
     const int end = p.rowptr[row + 1];
-    f32x2_t acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};      // packed fp32: one v_pk_fma_f32 per column pair
+    f32x2 acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};      // packed fp32: one v_pk_fma_f32 per column pair
     const uint16_t* xb = p.x + fl;
     for (int base = beg; base < end; base += 64) {
         const int cnt = (end - base) < 64 ? (end - base) : 64;
@@ -872,11 +684,11 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void spmm_vec_bf16_kernel(Spmm
             }
 #pragma unroll
             for (int k = 0; k < UNROLL; ++k) {
-                const f32x2_t s2 = {sc[k], sc[k]};
+                const f32x2 s2 = {sc[k], sc[k]};
                 const uint32_t q[4] = {g[k].x, g[k].y, g[k].z, g[k].w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x2_t v = {__uint_as_float(q[j] << 16), __uint_as_float(q[j] & 0xffff0000u)};
+                    const f32x2 v = {__uint_as_float(q[j] << 16), __uint_as_float(q[j] & 0xffff0000u)};
                     acc[j] = __builtin_elementwise_fma(s2, v, acc[j]);
                 }
             }
@@ -951,110 +763,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void spmm_vec_bf16_kernel(Spmm
     }
 }
 
-// ---- two rows per wavefront (round 6 experiment; PYGSD_BF16_PAIR=1) -----------------------------------------------------------
-// F = 64 bf16: a gathered row is 8 lanes x 16 bytes, so a wavefront's 64 lanes cover 8 entries per pass and 32 per unrolled
-// iteration of spmm_vec_bf16_kernel<8> -- a 26-entry row (C5b's average) leaves 6 of 32 slots idle and pays the whole prologue /
-// epilogue for itself.  Here each HALF of the wavefront owns a row: 4 entries per pass, 16 per iteration, the CSR entries of
-// both rows fetched by one load, one halving stage fewer in the reduce-scatter (bit 5 of the lane separates the rows), two
-// columns per lane stored as one dword.  Control flow is wavefront-uniform: both halves run max(len_0, len_1) worth of passes
-// with per-lane predicates.
-__global__ __launch_bounds__(kWavesPerBlock * 64) void spmm_vec_bf16_pair_kernel(SpmmBf16Args p)
-{
-    constexpr int UNROLL = 4;
-    const int lane = threadIdx.x & 63, hl = lane & 31, half = lane >> 5;
-    const int pair = static_cast<int>(blockIdx.x) * kWavesPerBlock + static_cast<int>(threadIdx.x >> 6);
-    const int row = 2 * pair + half;
-    if (2 * pair >= p.n_rows) return;
-    const bool live = row < p.n_rows;
-    const int sub = hl >> 3;                                   // which of the half's 4 concurrent entries
-    const int fl = (hl & 7) * 8;                               // first of this lane's 8 columns
-    const int beg = live ? p.rowptr[row] : 0;
-    const int end = live ? p.rowptr[row + 1] : 0;
-    const int len = end - beg;
-    const int other = __shfl_xor(len, 32);
-    const int longest = __builtin_amdgcn_readfirstlane(len > other ? len : other);
-    f32x2_t acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-    const uint16_t* xb = p.x + fl;
-    for (int off = 0; off < longest; off += 32) {
-        const int cnt = (len - off) < 32 ? (len - off) : 32;               // this half's entries of the pass (may be <= 0)
-        const int most = (longest - off) < 32 ? (longest - off) : 32;      // wavefront-uniform
-        int c = 0;
-        float w = 0.f;
-        if (hl < cnt) {
-            c = __builtin_nontemporal_load(p.col + beg + off + hl);
-            w = p.val ? __builtin_nontemporal_load(p.val + beg + off + hl) : 1.f;
-        }
-        for (int u = 0; u < most; u += 4 * UNROLL) {
-            uint4 g[UNROLL];
-            float sc[UNROLL];
-#pragma unroll
-            for (int k = 0; k < UNROLL; ++k) {
-                const int idx = u + k * 4 + sub;
-                const bool ok = idx < cnt;
-                const int src = (lane & 32) | (idx & 31);                   // the entry sits on a lane of this half
-                const int cj = __shfl(c, src);
-                const float t = __shfl(w, src);
-                sc[k] = ok ? t : 0.f;
-                g[k] = make_uint4(0u, 0u, 0u, 0u);
-                if (ok) g[k] = *reinterpret_cast<const uint4*>(xb + static_cast<int64_t>(cj) * p.ldx);
-            }
-#pragma unroll
-            for (int k = 0; k < UNROLL; ++k) {
-                const f32x2_t s2 = {sc[k], sc[k]};
-                const uint32_t q[4] = {g[k].x, g[k].y, g[k].z, g[k].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f32x2_t v = {__uint_as_float(q[j] << 16), __uint_as_float(q[j] & 0xffff0000u)};
-                    acc[j] = __builtin_elementwise_fma(s2, v, acc[j]);
-                }
-            }
-        }
-    }
-    // reduce-scatter over the half's 4 lane groups (lane bits 3 and 4): two columns per lane remain
-    const bool b3 = (lane & 8) != 0;
-    float r[4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float lo0 = acc[j].x, lo1 = acc[j].y, hi0 = acc[j + 2].x, hi1 = acc[j + 2].y;
-        r[2 * j] = add_ror8(b3 ? hi0 : lo0, b3 ? lo0 : hi0);
-        r[2 * j + 1] = add_ror8(b3 ? hi1 : lo1, b3 ? lo1 : hi1);
-    }
-    float v0 = add_swap16(r[0], r[2]), v1 = add_swap16(r[1], r[3]);
-    if (!live) return;
-    const int col = fl + ((lane >> 3) & 1) * 4 + ((lane >> 4) & 1) * 2;
-    const float d = p.mean ? static_cast<float>(len > 1 ? len : 1) : 1.f;
-    v0 = (p.mean ? v0 / d : v0) * p.alpha;
-    v1 = (p.mean ? v1 / d : v1) * p.alpha;
-    if (p.acc_f32) {
-        const float* zf = reinterpret_cast<const float*>(p.z);
-        if (zf) {
-            const float2 zz = *reinterpret_cast<const float2*>(zf + static_cast<int64_t>(row) * p.ldz + col);
-            v0 = fmaf(p.beta, zz.x, v0);
-            v1 = fmaf(p.beta, zz.y, v1);
-        }
-        *reinterpret_cast<float2*>(reinterpret_cast<float*>(p.y) + static_cast<int64_t>(row) * p.ldy + col) = make_float2(v0, v1);
-    } else {
-        float z0 = 0.f, z1 = 0.f;
-        if (p.z) {
-            const uint32_t zz = *reinterpret_cast<const uint32_t*>(p.z + static_cast<int64_t>(row) * p.ldz + col);
-            z0 = __uint_as_float(zz << 16);
-            z1 = __uint_as_float(zz & 0xffff0000u);
-        }
-        *reinterpret_cast<uint32_t*>(p.y + static_cast<int64_t>(row) * p.ldy + col) =
-            pack_bf16x2(fmaf(p.beta, z0, v0), fmaf(p.beta, z1, v1));
-    }
-}
-
-// 0 = one row per wavefront (default), 1 = two rows per wavefront at F = 64 (PYGSD_BF16_PAIR; measurement / A-B)
-int bf16_pair_mode()
-{
-    static const int mode = [] {
-        const char* e = getenv("PYGSD_BF16_PAIR");
-        return (e && e[0] == '1') ? 1 : 0;
-    }();
-    return mode;
-}
-
 int launch_spmm_bf16(const SpmmBf16Args& a, hipStream_t stream)
 {
     const dim3 block(kWavesPerBlock * 64);
@@ -1065,9 +773,6 @@ int launch_spmm_bf16(const SpmmBf16Args& a, hipStream_t stream)
         hipLaunchKernelGGL(spmm_vec_bf16_kernel<2>, dim3(gx), block, 0, stream, a);
     } else if (oct <= 4) {
         hipLaunchKernelGGL(spmm_vec_bf16_kernel<4>, dim3(gx), block, 0, stream, a);
-    } else if (oct == 8 && bf16_pair_mode() == 1) {
-        const unsigned gp = ((static_cast<unsigned>(a.n_rows) + 1u) / 2u + kWavesPerBlock - 1) / kWavesPerBlock;
-        hipLaunchKernelGGL(spmm_vec_bf16_pair_kernel, dim3(gp), block, 0, stream, a);
     } else if (oct <= 8) {
         hipLaunchKernelGGL(spmm_vec_bf16_kernel<8>, dim3(gx), block, 0, stream, a);
     } else if (oct <= 16) {
@@ -1219,30 +924,4 @@ extern "C" int pygsd_sddmm_coo_f32(const int32_t* ia, const int32_t* ib, int64_t
         hipLaunchKernelGGL(sddmm_kernel<false>, dim3(grid), dim3(256), 0, s, ia, ib, nnz, A, lda, B, ldb,
                            n_feat, out);
     return check_launch("sddmm_kernel");
-}
-
-extern "C" int pygsd_spmm2_k1_dense_f32(const int32_t* rowptr, const int32_t* col, const float* val_a, const float* val_b,
-                                        const float* Xa, const float* Xb, int64_t ldx, float* Ta, float* Tb, int64_t ldt,
-                                        const float* W, const float* bias, float* out_r, float* out_i, int64_t ldo,
-                                        int32_t n_rows, int64_t nnz_hint, void* stream)
-{
-    PYGSD_REQUIRE(n_rows >= 0, "pygsd_spmm2_k1_dense_f32: negative size");
-    if (n_rows == 0) return 0;
-    PYGSD_REQUIRE(rowptr && col && val_a && val_b && Xa && Xb && Ta && Tb && W && out_r && out_i,
-                  "pygsd_spmm2_k1_dense_f32: null pointer");
-    PYGSD_REQUIRE(ldx >= 64 && ldt >= 64 && ldo >= 64 && ldx % 4 == 0 && ldt % 4 == 0,
-                  "pygsd_spmm2_k1_dense_f32: 64 features, row strides >= 64 and multiples of 4");
-    PYGSD_REQUIRE(aligned16(Xa) && aligned16(Xb) && aligned16(Ta) && aligned16(Tb), "pygsd_spmm2_k1_dense_f32: feature matrices "
-                  "must be 16-byte aligned");
-    SpmmK1Args a{SpmmArgs{rowptr, col, val_a, val_b, Xa, Xb, Ta, Tb, nullptr, nullptr, ldx, ldt, 0, n_rows, 64, 1.f, 0.f, 0, 0},
-                 W, bias, out_r, out_i, ldo};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    ProfScope prof(PYGSD_K_SPMM2, s);
-    const dim3 block(kWavesPerBlock * 64);
-    const unsigned gx = (static_cast<unsigned>(n_rows) + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (nnz_hint >= static_cast<int64_t>(28) * n_rows)
-        hipLaunchKernelGGL(spmm2_k1_dense_kernel<true>, dim3(gx), block, 0, s, a);
-    else
-        hipLaunchKernelGGL(spmm2_k1_dense_kernel<false>, dim3(gx), block, 0, s, a);
-    return check_launch("spmm2_k1_dense_kernel");
 }

@@ -20,9 +20,6 @@
 namespace pygsd {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kMaxKB = 16;     // k-blocks: 32 bf16 / 16 fp32 columns each (one 16-byte load per lane)
 constexpr int kMaxSeg = 4;      // input column segments
 constexpr int kMaxOut = 8;      // output column segments
@@ -39,8 +36,6 @@ struct TallArgs {
 };
 
 __device__ __forceinline__ float bf16_value(uint32_t h) { return __uint_as_float(h << 16); }
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // two fp32 -> two bf16 in one dword, round to nearest even: one v_cvt_pk_bf16_f32 on gfx950
 __device__ __forceinline__ uint32_t pack2(float lo, float hi)
 {

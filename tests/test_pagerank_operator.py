@@ -23,7 +23,7 @@ def header_arg_counts():
     return out
 
 
-def test_pagerank_entries_declared_exported_and_bound():
+def test_pagerank_entries_declared_exported_and_bound_at_abi_20():
     from pytorch_geometric_signed_directed_amd import _cabi
     counts = header_arg_counts()
     assert sorted(counts) == sorted(ENTRIES)
@@ -32,7 +32,7 @@ def test_pagerank_entries_declared_exported_and_bound():
         assert hasattr(lib, name), name
         assert name in _cabi.PROTOTYPES, name
         assert len(_cabi.PROTOTYPES[name][1]) == counts[name], name
-    assert _cabi.ABI_VERSION == 19 and _cabi.lib().pygsd_version() == 19
+    assert _cabi.ABI_VERSION == 20 and _cabi.lib().pygsd_version() == 20
 
 
 def test_pagerank_work_size_matches_header():
