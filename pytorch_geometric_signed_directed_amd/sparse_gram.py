@@ -70,6 +70,10 @@ def gram(b: SparseValues, bt: SparseValues, scale: Optional[Tensor] = None, *, l
         scale = scale.contiguous()
     caps = _tier_caps()
     limit = caps[-1] if lds_limit is None else max(0, min(int(lds_limit), caps[-1]))
+    if b.csr.nnz == 0:   # no products (and no column buffer for pygsd_gram_count to read): C is empty
+        return SparseValues(CSR(n_out, n_out, 0, torch.zeros(n_out + 1, dtype=torch.int32, device=dev),
+                                torch.empty(0, dtype=torch.int32, device=dev), None),
+                            torch.empty(0, dtype=torch.float32, device=dev))
     lib = _cabi.lib()
     with _cabi.on_device(dev):
         s = stream_ptr()

@@ -6,6 +6,7 @@ import pytest
 import scipy.sparse as sp
 import torch
 
+import operator_bars as B
 from conftest import load_golden
 from test_second_order import FEATURE_CASES, DEGREE_CASES, check_features, feature_inputs
 
@@ -31,11 +32,12 @@ def restated(ei, size, w=None):
     return out
 
 
-def assert_matches(index, value, m):
+def assert_matches(index, value, m, ref):
+    """Structure equal to scipy's, and every element within its own bar of the float64 arbiter `ref`
+    (tests/operator_bars.py): one float32 rounding of a float64 sum, plus the scales' float32 sums for the features."""
     coo = m.tocoo()
     assert np.array_equal(index.cpu().numpy(), np.stack([coo.row, coo.col])), "structure differs from scipy"
-    err = np.abs(value.cpu().numpy().astype(np.float64) - coo.data) / (1 + np.abs(coo.data))
-    assert err.max(initial=0) <= 1e-5, err.max()
+    B.check_elements("gram", index.cpu().numpy(), value.cpu().numpy(), ref)
 
 
 def same(a, b):
@@ -61,8 +63,9 @@ def test_features_dsbm_against_scipy_and_deterministic():
     t_ei, t_w = torch.from_numpy(ei).to(DEV), torch.from_numpy(w).to(DEV)
     got = directed_features_in_out(t_ei, 50_000, t_w)
     a_in, a_out = restated(ei, 50_000, w)
-    assert_matches(got[1], got[2], a_in)
-    assert_matches(got[3], got[4], a_out)
+    r_in, r_out = B.features_refs(ei, 50_000, w)
+    assert_matches(got[1], got[2], a_in, r_in)
+    assert_matches(got[3], got[4], a_out, r_out)
     assert same(got, directed_features_in_out(t_ei, 50_000, t_w))                   # bit-identical rerun
     assert same(got, directed_features_in_out(t_ei, 50_000, t_w, lds_limit=0))      # every row on the global path
     assert same(got, directed_features_in_out(t_ei, 50_000, t_w, lds_limit=1024))   # smallest tier + global
@@ -95,7 +98,7 @@ def test_gram_hub_row_beyond_lds():
     c[c == 0] = 1
     scale = torch.from_numpy(1.0 / c).to(DEV)
     got = gram(a, at, scale)
-    assert_matches(coo_rows(got), got.val, a_in)
+    assert_matches(coo_rows(got), got.val, a_in, B.gram_ref(ei[0], ei[1], w, n, n, 1.0 / c))
     for limit in (0, 1024, 4096, 1 << 30):
         other = gram(a, at, scale, lds_limit=limit)
         assert torch.equal(other.csr.rowptr, got.csr.rowptr) and torch.equal(other.csr.col, got.csr.col), limit
@@ -129,8 +132,9 @@ def test_features_every_lds_tier_and_global_path():
     t_ei, t_w = torch.from_numpy(ei).to(DEV), torch.from_numpy(w).to(DEV)
     got = directed_features_in_out(t_ei, n, t_w)
     a_in, a_out = restated(ei, n, w)
-    assert_matches(got[1], got[2], a_in)
-    assert_matches(got[3], got[4], a_out)
+    r_in, r_out = B.features_refs(ei, n, w)
+    assert_matches(got[1], got[2], a_in, r_in)
+    assert_matches(got[3], got[4], a_out, r_out)
     for limit in (0, 1024, 4096, 8192):
         assert same(got, directed_features_in_out(t_ei, n, t_w, lds_limit=limit)), limit
 
@@ -246,3 +250,104 @@ def test_second_directed_adj_cuda_matches_host_path_mid_size():
         assert ((got_v.cpu() - want_v).abs() / (1 + want_v.abs())).max().item() <= 5e-6
         forced = _second_directed_adj_device(ei.to(DEV), 5_000, None if wt is None else wt.to(DEV), lds_limit=0)
         assert torch.equal(forced[0], got_i) and torch.equal(forced[1], got_v)
+
+
+# ---- planted boundaries of the Gram product's tiers, hub batches and the int64 scan ----------------------------------
+def squares(p):
+    """p as a sum of squares (greedy): run lengths L_k with sum L_k^2 = p."""
+    out = []
+    while p:
+        root = int(np.sqrt(p))
+        out.append(root)
+        p -= root * root
+    return out
+
+
+def gram_all_limits(b, bt, scale=None):
+    """gram at lds_limit None, 0 and every tier cap: all bit-identical; returns the default."""
+    from pytorch_geometric_signed_directed_amd.sparse_gram import _tier_caps, gram
+    got = gram(b, bt, scale)
+    for limit in [0] + _tier_caps():
+        other = gram(b, bt, scale, lds_limit=limit)
+        assert same((got.csr.rowptr, got.csr.col, got.val), (other.csr.rowptr, other.csr.col, other.val)), limit
+    return got
+
+
+@pytest.mark.parametrize("tier", [0, 1, 2])
+def test_gram_rows_at_each_tier_edge(tier):
+    """Rows of 1, cap - 1, cap and cap + 1 products for cap = pygsd_gram_tier_cap(tier): cap products fill the bitonic
+    sort with no padding, cap + 1 is the next tier's (or the global path's) first row.
+    - one run: every product in one column (L_k duplicates of (k, 0), sum L_k^2 = p), integer weights: exact;
+    - distinct columns: one row of B with p entries, so C = b b^T and every element is one float32 rounding of an exact
+      float64 product: bit-exact."""
+    from pytorch_geometric_signed_directed_amd import _cabi
+    from pytorch_geometric_signed_directed_amd.sparse_gram import coo_rows, from_coo
+    cap = _cabi.lib().pygsd_gram_tier_cap(tier)
+    rng = np.random.default_rng(tier)
+    for p in (1, cap - 1, cap, cap + 1):
+        runs = squares(p)
+        r = np.repeat(np.arange(len(runs)), runs)
+        c = np.zeros(r.size, np.int64)
+        w = rng.integers(1, 4, r.size).astype(np.float32)
+        t = [torch.from_numpy(x).to(DEV) for x in (r, c, w)]
+        got = gram_all_limits(*from_coo(t[0], t[1], t[2], len(runs), 1))
+        ref = B.gram_ref(r, c, w, len(runs), 1, exact=True)
+        B.check_elements(f"one run p={p}", coo_rows(got).cpu().numpy(), got.val.cpu().numpy(), ref)
+        assert got.csr.nnz == 1 and np.sum([x * x for x in runs]) == p
+        b = torch.from_numpy(rng.uniform(0.5, 2.0, p).astype(np.float32)).to(DEV)
+        cols = torch.arange(p, dtype=torch.int64, device=DEV)
+        got = gram_all_limits(*from_coo(torch.zeros_like(cols), cols, b, 1, p))
+        want = (b.double()[:, None] * b.double()[None, :]).float()
+        assert torch.equal(got.csr.rowptr.long(), torch.arange(p + 1, device=DEV) * p), p
+        assert torch.equal(got.csr.col.view(p, p).long(), cols.expand(p, p)), p
+        assert torch.equal(got.val.view(p, p), want), p
+        del got, want
+
+
+def test_gram_hub_batches_bit_identical(monkeypatch):
+    """The global path with HUB_BATCH_PRODUCTS = 3 000: several hubs share a batch (the batch-relative key h << 32 | j
+    restarts at every batch), one hub (column 400, ~10 000 products) is larger than a batch, and one (column 401) cancels
+    to no entry at all (rows 200 and 201 identical, their scales +1 and -1).  Integer weights, scales +-1 / powers of
+    two: exact, so held bit-exactly to float64 and bit-identical to the default batching."""
+    from pytorch_geometric_signed_directed_amd import sparse_gram
+    from pytorch_geometric_signed_directed_amd.sparse_gram import coo_rows, from_coo, gram
+    rng = np.random.default_rng(17)
+    rows, cols = [], []
+    for k in range(200):
+        cs = rng.choice(400, 50, replace=False)
+        rows += [k] * 51
+        cols += list(cs) + [400]
+    twin = list(402 + rng.choice(600, 599, replace=False)) + [401]
+    rows += [200] * 600 + [201] * 600
+    cols += twin + twin
+    r, c = np.array(rows), np.array(cols)
+    w = rng.integers(1, 4, r.size).astype(np.float32)
+    w[r == 201] = w[r == 200]
+    scale = 2.0 ** rng.integers(-2, 3, 202).astype(np.float64)
+    scale[200], scale[201] = 1.0, -1.0
+    t = [torch.from_numpy(x).to(DEV) for x in (r, c, w)]
+    b, bt = from_coo(t[0], t[1], t[2], 202, 1002)
+    s = torch.from_numpy(scale).to(DEV)
+    want = gram(b, bt, s, lds_limit=1024)
+    counts = np.bincount(c, weights=np.bincount(r)[r], minlength=1002)
+    assert counts[400] > 3000 and counts[401] > 1024 and (counts[:400] > 1024).sum() > 100
+    monkeypatch.setattr(sparse_gram, "HUB_BATCH_PRODUCTS", 3000)
+    got = gram(b, bt, s, lds_limit=1024)
+    assert same((got.csr.rowptr, got.csr.col, got.val), (want.csr.rowptr, want.csr.col, want.val))
+    assert int(got.csr.rowptr[402] - got.csr.rowptr[401]) == 0
+    ref = B.gram_ref(r, c, w, 202, 1002, scale, exact=True)
+    B.check_elements("hub batches", coo_rows(got).cpu().numpy(), got.val.cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 4097, (1 << 20) + 5])
+def test_scan_i64_against_cumsum(n):
+    """pygsd_scan_i64 through sparse_gram._scan: exclusive scan with the total at [n], counts up to 2^40 so that the
+    running sums pass 2^32 (the int64 claim), bit-exact against numpy."""
+    from pytorch_geometric_signed_directed_amd.sparse_gram import _scan
+    rng = np.random.default_rng(n)
+    counts = rng.integers(0, 1 << 40, n, dtype=np.int64)
+    got = _scan(torch.from_numpy(counts).to(DEV)).cpu().numpy()
+    want = np.concatenate([[0], np.cumsum(counts)])
+    assert got.dtype == np.int64 and np.array_equal(got, want)
+    if n > 256:
+        assert want[-1] > (1 << 32)
