@@ -353,6 +353,31 @@ int pygsd_pagerank_scale(const int32_t* rowptr, const int32_t* col, const double
                          double* dis, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Typed triangle-motif counts of SDGNN (nn/signed/SDGNN.py: build_adj_lists / get_features) and SiGAT
+ * (nn/signed/SiGAT.py: get_tri_features).  csrc/motifs.hip.
+ * Input: the sorted unique keys u * n + v (int64) of U = P u N, P / N the distinct (source, target) pairs of
+ * positive / negative sign, and flags[i] (uint8): bit 0 = key i in P, bit 1 = key i in N.
+ *   pygsd_motif_workspace      : device workspace of pygsd_motif_neighbourhoods.  Refuses 2 * n_keys > 2^31 - 1.
+ *   pygsd_motif_neighbourhoods : the typed CSR: row u lists every w with (u, w) or (w, u) in U once, ascending
+ *                                int32 columns, mask (uint8) bit 0: w in out_P(u), 1: out_N(u), 2: in_P(u),
+ *                                3: in_N(u).  col / mask hold room for 2 * n_keys entries; rowptr[n] is the
+ *                                number written.
+ *   pygsd_motif_count          : for the keys ids[0 .. n_ids) (ids NULL: every key, n_ids = n_keys),
+ *                                counts[16 i + k] (int32 [n_keys, 16], row-major, 16-byte aligned) = counter
+ *                                k = 4 g + 2 x + y of key i = (u, v), x, y = 0 for P, 1 for N:
+ *                                g = 0: |out_X(u) & in_Y(v)|, 1: |out_X(u) & out_Y(v)|, 2: |in_X(u) & out_Y(v)|,
+ *                                3: |in_X(u) & in_Y(v)| -- the entries (u, v) of X Y, X Y^T, X^T Y^T, X^T Y.
+ *                                The shorter typed list is binary-searched in the longer.  tier 0: one lane per
+ *                                key; tier 1: one wavefront per key.  Both give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+int pygsd_motif_workspace(int64_t n_keys, size_t* bytes);
+int pygsd_motif_neighbourhoods(const int64_t* keys, const uint8_t* flags, int64_t n_keys, int32_t n, int32_t* rowptr,
+                               int32_t* col, uint8_t* mask, void* workspace, size_t workspace_bytes, void* stream);
+int pygsd_motif_count(const int64_t* keys, int64_t n_keys, int32_t n, const int32_t* rowptr, const int32_t* col,
+                      const uint8_t* mask, const int32_t* ids, int64_t n_ids, int32_t tier, int32_t* counts,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (Signed) magnetic Laplacian build on the device -- utils/directed/get_magnetic_Laplacian.py:47-85,
  * utils/general/get_magnetic_signed_Laplacian.py:47-90 (called from MagNetConv.__norm__ :100-103 /
  * MSConv.__norm__ :99-102 on EVERY forward unless cached=True).

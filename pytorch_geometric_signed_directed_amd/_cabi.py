@@ -97,6 +97,11 @@ PROTOTYPES = {
     "pygsd_pagerank_union_emit": (c_int32, [c_void_p] * 11 + [c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                                              c_void_p, c_void_p]),
     "pygsd_pagerank_scale": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pygsd_motif_workspace": (c_int32, [c_int64, ctypes.POINTER(c_size_t)]),
+    "pygsd_motif_neighbourhoods": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_size_t, c_void_p]),
+    "pygsd_motif_count": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                    c_int32, c_void_p, c_void_p]),
     "pygsd_maglap_workspace": (c_int32, [c_int64, ctypes.POINTER(c_size_t)]),
     "pygsd_maglap_sort": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
     "pygsd_maglap_merge": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_size_t,

@@ -643,8 +643,9 @@ class SDGNN(nn.Module):
     """nn/signed/SDGNN.py:66-267: trainable node embeddings through `layer_num` SDRLayers (four GATConv
     aggregators: positive out / in, negative out / in neighbourhoods), objective = sign + lamb_d * direction +
     lamb_t * triangle loss.  The reference enumerates neighbour sets and triangle motifs with Python dict / set
-    loops; here the same sets are sparse 0/1 matrices and the 12 motif counts are sparse products (host side, once
-    at construction -- not part of the device path)."""
+    loops.  A CUDA `edge_index_s` builds them on the device (motifs.py, csrc/motifs.hip: per-edge typed triangle
+    counts by set intersection), including the triangle loss's per-edge weights; a CPU one builds them on the host
+    as sparse 0/1 matrices and sparse products."""
 
     def __init__(self, node_num: int, edge_index_s, in_dim: int = 20, out_dim: int = 20, layer_num: int = 2,
                  init_emb: Optional[torch.Tensor] = None, init_emb_grad: bool = True, lamb_d: float = 5.0,
@@ -671,6 +672,12 @@ class SDGNN(nn.Module):
         self.loss_sign = Sign_Product_Entropy_Loss()
         self.loss_direction = Sign_Direction_Loss(emb_dim=out_dim)
         self.loss_tri = Sign_Triangle_Loss(emb_dim=out_dim, edge_weight=self.tri_weight)
+        if self._device_weights is not None:     # the loss's per-edge weights, looked up on the device, no scipy
+            from .. import motifs
+            nb, w = self._device_weights
+            for ei in (self.pos_edge_index, self.neg_edge_index):
+                self.loss_tri._memo.put((ei,), "triangle weights", motifs.lookup(nb, w, ei).reshape(-1, 1))
+        self._device_weights = None
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -685,7 +692,18 @@ class SDGNN(nn.Module):
         the entries of the products X Y, X Y^T, X^T Y^T, X^T Y (X, Y in {P, N}); its masks select
           positive edge: PP + PP^T + NN^T + N^T N^T + P^T P + N^T N
           negative edge: PN + NP + NP^T + P^T N^T + N^T P^T + P^T N
-        and an edge listed with both signs keeps the negative count (the reference writes it last)."""
+        and an edge listed with both signs keeps the negative count (the reference writes it last).
+        A CUDA `edge_index_s` takes the device path (motifs.py): the same sets and counts by per-edge set intersection,
+        every list in ascending (node, neighbour) order, `tri_weight` from one device -> host copy with every pair of
+        P u N stored (explicit zeros included).  A CPU one runs the scipy products below."""
+        self._device_weights = None
+        if edge_index_s.is_cuda:
+            from .. import motifs
+            nb = motifs.signed_neighbourhoods(edge_index_s, self.node_num)
+            w = motifs.sdgnn_weights(nb, motifs.motif_counts(nb))
+            self.tri_weight = motifs.tri_weight_matrix(nb, w)
+            self._device_weights = (nb, w)
+            return motifs.sdgnn_lists(nb)
         P, N = _signed_matrices(edge_index_s, self.node_num)
         d = _motif_counts(P, N)
         m_pos = d[0] + d[4] + d[7] + d[11] + d[12] + d[15]        # mask [1,0,0,0, 1,0,0,1, 0,0,0,1, 1,0,0,1]
@@ -719,7 +737,9 @@ class SiGAT(nn.Module):
     """nn/signed/SiGAT.py:13-203: one GATConv aggregator per motif neighbourhood -- positive / negative
     (undirected, out, in) and, for the positive and for the negative out-edges, the 16 subsets closed by at
     least one triangle of each type -- concatenated with the embedding, then Linear-Tanh-Linear; objective =
-    link-sign product loss.  The 38 neighbourhoods come from the same sparse products as SDGNN's weights."""
+    link-sign product loss.  The 38 neighbourhoods come from the same motif counts as SDGNN's weights: built on the
+    device for a CUDA `edge_index_s` (motifs.py; every list in ascending order), by sparse products on the host for a
+    CPU one."""
 
     def __init__(self, node_num: int, edge_index_s, in_dim: int = 20, out_dim: int = 20,
                  init_emb: Optional[torch.Tensor] = None, init_emb_grad: bool = True, **kwargs):
@@ -745,6 +765,10 @@ class SiGAT(nn.Module):
         self.reset_parameters()
 
     def build_edge_lists(self, edge_index_s):
+        if edge_index_s.is_cuda:
+            from .. import motifs
+            nb = motifs.signed_neighbourhoods(edge_index_s, self.node_num)
+            return motifs.sigat_lists(nb, motifs.motif_counts(nb))
         P, N = _signed_matrices(edge_index_s, self.node_num)
         d = _motif_counts(P, N)
 
